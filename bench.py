@@ -296,6 +296,43 @@ def _last_line_helper():
         return None
 
 
+DUMP_SAMPLE_ELEMS = 8 << 20     # --dump-outputs: float32 weight elements written in all (32 MB; metrics and the per-tensor floor add little)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def step_outputs(ag, mets):
+    """--dump-outputs: what a caller of the timed step receives, copied to the host -- every numeric metric the step returns
+    (float64) and the weights it has just trained (float32).  A tensor larger than its share of DUMP_SAMPLE_ELEMS is written as a
+    fixed sample of its flattened elements, drawn from a seed derived from its name (sorted indices: the same from run to run)."""
+    import zlib
+    out = {}
+    for k, v in mets.items():
+        if torch.is_tensor(v):
+            out['metric.' + k] = v.detach().to(torch.float64).cpu().numpy()
+        elif isinstance(v, (bool, int, float, np.number)):
+            out['metric.' + k] = np.asarray(v, np.float64)
+    params = {k: v for k, v in ag.state_dict().items() if torch.is_floating_point(v)}
+    frac = min(1.0, DUMP_SAMPLE_ELEMS / max(1, sum(v.numel() for v in params.values())))
+    for k, v in params.items():
+        flat = v.detach().reshape(-1)
+        n = flat.numel()
+        keep = min(n, max(1024, int(n * frac)))
+        if keep < n:
+            idx = np.sort(np.random.Generator(np.random.PCG64(zlib.crc32(k.encode()))).choice(n, keep, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        out['param.' + k] = flat.to(torch.float32).cpu().numpy()
+    nbytes = sum(a.nbytes for a in out.values())
+    assert nbytes <= DUMP_MAX_BYTES, f'--dump-outputs: {nbytes} bytes, over the {DUMP_MAX_BYTES} limit'
+    return out
+
+
+def write_outputs(d, arrays):
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name.replace('/', '_') + '.npy'), a)
+    print(f'[bench] --dump-outputs: {len(arrays)} arrays of the last timed step in {d}', file=sys.stderr)
+
+
 def main():
     global _real_stdout
     ap = argparse.ArgumentParser()
@@ -313,6 +350,9 @@ def main():
     ap.add_argument('--no-fp32-mode', action='store_true', help='skip the comparison run with fp32 MFMAs throughout')
     ap.add_argument('--no-traffic', action='store_true', help='skip the two rocprofv3 PMC passes (HBM bytes per GEMM launch)')
     ap.add_argument('--dump-gemm', default='')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed steps, write what the last one computed (its metrics and the trained weights, a fixed '
+                         'sample of the larger tensors) as DIR/<name>.npy')
     ap.add_argument('--sync-each-step', action='store_true', help='diagnostic: synchronise after every step (the host never enqueues ahead of the GPU)')
     ap.add_argument('--no-overlap', action='store_true', help='keep the connector updates on the main stream')
     ap.add_argument('--input', default='replay', choices=['replay', 'fixed'],
@@ -327,6 +367,8 @@ def main():
                     help='data parallel: auto = collectives captured inside the graph when the backend is RCCL (falls back to '
                          'cuts, then eager); cut = collectives eager between graph segments')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     global PEAK_F32_MFMA_TFLOPS
     if args.precision == 16:
         PEAK_F32_MFMA_TFLOPS = PEAK_BF16_MFMA_TFLOPS   # the roofline of the bf16 mode is priced against the bf16 peak
@@ -504,6 +546,9 @@ def main():
             if graphed is not None:
                 graphed = GraphedStep(ag, batch, step_fn, warmup=1, collectives='cut')
                 run_step = stepper(graphed)
+    # (before the eager and fp32-MFMA legs below, which go on training the same weights)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, step_outputs(ag, mets))
     loss_key = 'model_loss' if 'model_loss' in mets else 'imag_critic_loss'      # (configs[4] has no world-model phase)
     loss = float(mets[loss_key])
     assert np.isfinite(loss), (loss_key, loss)
@@ -646,6 +691,8 @@ def main():
             if np.isfinite(l2) and dt2 < dt:             # (all ranks hold the same max-over-ranks times: the same decision everywhere)
                 ingraph_outcome = f'adopted ({1e3 * dt2 / args.steps:.2f} ms/step against {1e3 * dt / args.steps:.2f} with cuts)'
                 dt, mets, loss, graphed, launch_mode = dt2, mets2, l2, g2, 'hipGraph replay, collectives ingraph'
+                if args.dump_outputs and rank == 0:
+                    write_outputs(args.dump_outputs, step_outputs(ag, mets))
             else:
                 ingraph_outcome = f'slower ({1e3 * dt2 / args.steps:.2f} ms/step against {1e3 * dt / args.steps:.2f} with cuts): not adopted'
                 print(f'[bench] in-graph collectives: {1e3 * dt2 / args.steps:.2f} ms/step, cut mode {1e3 * dt / args.steps:.2f}: keeping the cut mode', file=sys.stderr)

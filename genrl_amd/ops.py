@@ -24,6 +24,13 @@ def _p(t):
     return t.data_ptr()
 
 
+def _on_gpu(*ts):
+    """operands a wrapper hands over as raw addresses (strided or offset, so not through _p): the same refusal, before any launch"""
+    for t in ts:
+        if not t.is_cuda:
+            raise GenrlHipError('genrl_amd ops need tensors on the MI355X (no CPU fallback)')
+
+
 # how `precision: 32` runs its big-tile GEMMs: 'f32' = fp32 MFMA; 'bf16x3-big' / 'bf16x3' = fp32 operands split exactly into
 # three bf16 terms, six bf16 MFMA products, fp32 accumulation (fp32-equivalent error; GENRL_GEMM_MODE=0|2|3 overrides)
 F32_MODE = {'0': 'f32', '2': 'bf16x3-big', '3': 'bf16x3'}.get(os.environ.get('GENRL_GEMM_MODE', ''), 'bf16x3-big')
@@ -183,6 +190,7 @@ def _ws(n, dev):
 
 def sgemm(A, a_rs, a_ks, B, b_rs, b_ks, C, ldc, bias, M, N, K, accumulate=False, a_off=0, b_off=0, c_off=0):
     """C[m,n] (+)= sum_k A[m*a_rs+k*a_ks] B[n*b_rs+k*b_ks] (+bias[n]); offsets in elements."""
+    _on_gpu(A, B, C)
     if gemm_profile is not None:        # bench.py: HIP events around every launch of the GEMM kernel
         e0 = torch.cuda.Event(enable_timing=True); e0.record()
     nws = lib().genrl_sgemm_ws_floats(M, N, K)
@@ -199,6 +207,7 @@ def sgemm(A, a_rs, a_ks, B, b_rs, b_ks, C, ldc, bias, M, N, K, accumulate=False,
 def sgemm_conv(A, a_rs, a_ks, B, b_rs, b_ks, C, ldc, bias, M, N, K, which, img, accumulate=False):
     """sgemm with operand `which` (1 = A, 2 = B) read as the implicit stride-2 patch matrix of the NHWC
     image img = (H, W, C, k) (include/genrl_hip.h: genrl_sgemm_conv) — no materialised im2col."""
+    _on_gpu(A, B, C)
     if gemm_profile is not None:
         e0 = torch.cuda.Event(enable_timing=True); e0.record()
     nws = lib().genrl_sgemm_ws_floats(M, N, K)
@@ -221,6 +230,7 @@ def colsum(x2d, out=None, accumulate=False, ld=None):
 
 
 def copy2d(src, lds, dst, ldd, rows, cols, rowscale=None, accumulate=False, src_off=0, dst_off=0):
+    _on_gpu(src, dst)
     check(lib().genrl_copy2d(src.data_ptr() + 4 * src_off, lds, dst.data_ptr() + 4 * dst_off, ldd, rows, cols,
                              _p(rowscale), int(accumulate), _stream()), 'copy2d')
 

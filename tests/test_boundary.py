@@ -44,6 +44,23 @@ def test_no_cpu_fallback():
         ops.linear(torch.randn(4, 8), torch.randn(3, 8), None)
 
 
+def test_no_cpu_fallback_refuses_before_any_launch(monkeypatch):
+    """as on a machine WITH a GPU (the current stream resolves): host tensors are refused before the library is reached, so no kernel
+    is ever launched on host addresses"""
+    from genrl_amd import ops, _lib
+
+    class NoLib:
+        def __getattr__(self, name):
+            raise AssertionError(f'library reached ({name}) with host tensors')
+    monkeypatch.setattr(ops, '_stream', lambda: 0)
+    monkeypatch.setattr(ops, 'lib', lambda: NoLib())
+    for f in (lambda: ops.linear(torch.randn(4, 8), torch.randn(3, 8), None),
+              lambda: ops.linear(torch.randn(4, 8), torch.randn(3, 8), torch.randn(3)),
+              lambda: ops.copy2d(torch.randn(4, 8), 8, torch.empty(4, 8), 8, 4, 8)):
+        with pytest.raises(_lib.GenrlHipError):
+            f()
+
+
 def test_agent_is_picklable():
     import io
     from genrl_amd import config
