@@ -268,7 +268,10 @@ __global__ __launch_bounds__(256) void cosdist_rows_kernel(const float* __restri
     xnorm[row] = nx;
   }
 }
-// dx[row] = -(g / R) * (c_hat - cos * r) / ||x||   with c_hat = c / ||c||, r = x / ||x||
+// dx[row] = -(g / R) * (c_hat / max(||r||, 1e-8) - cos * r / ||r||^2) / max(||x||, 1e-12)   with c_hat = c / max(||c||, 1e-8),
+// r = x / max(||x||, 1e-12): the derivative of both clamps as torch takes it.  For every x with ||x|| >= 1e-12, ||r|| is exactly 1
+// and this is (c_hat - cos * r) / ||x||; on an all-zero x row the forward's 1e-8 clamp of ||r|| scales c_hat by 1e8 and the
+// projection term (d||r|| = 0 inside the clamp) drops out.
 __global__ __launch_bounds__(256) void cosdist_bwd_kernel(const float* __restrict__ x, const float* __restrict__ c,
                                                           const float* __restrict__ cosv, const float* __restrict__ xnorm,
                                                           const float* __restrict__ g, float* __restrict__ dx, long R, int E) {
@@ -276,12 +279,16 @@ __global__ __launch_bounds__(256) void cosdist_bwd_kernel(const float* __restric
   const long row = blockIdx.x;
   const float* xr = x + row * E;
   const float* cr = c + row * E;
-  float sc = 0.f;
-  for (int i = threadIdx.x; i < E; i += 256) sc += cr[i] * cr[i];
+  float sc = 0.f, sx = 0.f;
+  for (int i = threadIdx.x; i < E; i += 256) { sc += cr[i] * cr[i]; sx += xr[i] * xr[i]; }
   sc = block_sum_256(sc, red);
-  const float inv_c = 1.0f / fmaxf(sqrtf(sc), 1e-8f), nx = xnorm[row], cs = cosv[row];
+  sx = block_sum_256(sx, red);
+  const float nx = xnorm[row], cs = cosv[row];
+  const float rn = nx > 1e-12f ? 1.0f : sqrtf(sx) / nx;                  // ||r||: 1 unless the 1e-12 clamp of ||x|| acted
+  const float inv_c = 1.0f / fmaxf(sqrtf(sc), 1e-8f) / fmaxf(rn, 1e-8f);
+  const float proj = rn >= 1e-8f ? cs / (rn * rn) : 0.f;
   const float k = -g[0] / (float)R / nx;
-  for (int i = threadIdx.x; i < E; i += 256) dx[row * E + i] = k * (cr[i] * inv_c - cs * (xr[i] / nx));
+  for (int i = threadIdx.x; i < E; i += 256) dx[row * E + i] = k * (cr[i] * inv_c - proj * (xr[i] / nx));
 }
 
 }  // namespace

@@ -99,6 +99,19 @@ def test_c5_datafree_256_rows_horizon_15_vs_oracle(operands, monkeypatch):
     outputs in test_gpu_datafree.py.)  Runs under the PRODUCT's operand policy (round 6: plane operands from 192 rows:
     sampled latents may differ on near-ties, at the rate the c3 / c4 full-size cases accept) and with the explicit switch
     back to fp32 operands at this size (GENRL_PLANES_MIN_ROWS=320: every sampled latent exact)."""
+    _c5_case(operands, 10, monkeypatch)
+
+
+@pytest.mark.parametrize('operands', ['default_planes_from_256_rows', 'exact_fp32_switch'])
+@pytest.mark.parametrize('A', [12, 32])
+def test_c5_datafree_action_width_vs_oracle(A, operands, monkeypatch):
+    """The c5 case above at action widths the goldens never run: A = 12 (the quadruped tasks; the action rows of
+    roundup4(A) columns have no padding column, and the fused actor head takes its MAXO = 32 forward / MAXO = 16 backward
+    instantiations) and A = 32 (the largest width the fused head accepts: MAXO = 64 / 32)."""
+    _c5_case(operands, A, monkeypatch)
+
+
+def _c5_case(operands, A, monkeypatch):
     from genrl_amd import config, noise as gnoise
     from genrl_amd.agent import dreamer_utils as common
     from genrl_amd import ops_planes
@@ -108,7 +121,7 @@ def test_c5_datafree_256_rows_horizon_15_vs_oracle(operands, monkeypatch):
         monkeypatch.delenv('GENRL_PLANES_MIN_ROWS', raising=False)    # the product's default threshold (192 rows)
         assert ops_planes.min_rows() == 192
     torch.set_num_threads(min(16, os.cpu_count() or 1))
-    BS, BL, A, S, K, H, seed = 16, 16, 10, 32, 32, 15, 8
+    BS, BL, S, K, H, seed = 16, 16, 32, 32, 15, 8
     zero = dict(lr=0.0, wd=0.0)
     cfg = config.default_cfg(BS, BL, device='cuda', imag_horizon=H, model_opt=zero, actor_opt=zero, critic_opt=zero)
     ag = config.make_agent(cfg, act_dim=A)
