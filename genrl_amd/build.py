@@ -34,7 +34,8 @@ def needs_build():
     if not os.path.exists(OUT):
         return True
     t = os.path.getmtime(OUT)
-    return any(os.path.getmtime(_src(d)) > t for d in SRC) or _hdr_time() > t
+    # an object older than its source (the source edited while it compiled) is stale even under a newer library
+    return any(os.path.getmtime(_src(d)) > t for d in SRC) or _hdr_time() > t or any(_stale(d) for d in SRC)
 
 
 def build(force=False, verbose=True, extra=()):

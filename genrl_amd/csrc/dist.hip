@@ -383,12 +383,14 @@ __global__ __launch_bounds__(256) void kl_balance_fwd_kernel(const float* __rest
     *loss = mix * m + (1.0f - mix) * m;
   }
 }
-// per-row upstream gradients of the two KL sides: clamp_min passes the gradient where kl >= free
+// per-row upstream gradients of the two KL sides: torch.maximum(kl, free) passes the gradient where kl > free and
+// half of it at a tie (kl == free)
 __global__ void kl_balance_bwd_kernel(const float* __restrict__ kl, const float* __restrict__ gloss, long R, float mix,
                                       float free_, float* __restrict__ gp, float* __restrict__ gq) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= R) return;
-  const float g = (kl[i] >= free_) ? gloss[0] / (float)R : 0.f;
+  const float gm = gloss[0] / (float)R;
+  const float g = kl[i] > free_ ? gm : (kl[i] == free_ ? 0.5f * gm : 0.f);
   gp[i] = mix * g;
   gq[i] = (1.0f - mix) * g;
 }

@@ -12,12 +12,14 @@ __global__ __launch_bounds__(256) void sqnorm_partial_kernel(const float* __rest
   __shared__ float red[8];
   float a = 0.f;
   const long stride = (long)gridDim.x * 256 * 4;
+  const bool al16 = (reinterpret_cast<uintptr_t>(g) & 15) == 0;   // a view that starts mid-quad: scalar loads only
   for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += stride) {
-    if (i + 3 < n) {
+    if (al16 && i + 3 < n) {
       const float4 v = *reinterpret_cast<const float4*>(g + i);
       a += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
     } else {
-      for (long j = i; j < n; ++j) a += g[j] * g[j];
+      const long e = min(i + 4, n);
+      for (long j = i; j < e; ++j) a += g[j] * g[j];
     }
   }
   a = block_sum_256(a, red);

@@ -12,16 +12,14 @@ per-row scales for a reduction over rows).  Each K sits about ten times above th
 an MI355X): a subtly wrong kernel (variance over N - 1, a dropped slice, a dropped partial row, a lane off by one) fails by
 orders of magnitude.  Outputs are prefilled with NaN, so an element a kernel never writes fails; every buffer has padding
 columns and a guard row, which must come back bit-identical."""
-import math
-
 import pytest
 import torch
 import torch.nn.functional as F
 
+from f64check import PAD, checker, in_buf, out_buf, untouched
+
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24          # fp32 unit roundoff
-PAD = -1.2345678e33     # what the padding columns and guard rows of output buffers hold
 EINVAL = 1
 
 # K per checked quantity (see the module docstring)
@@ -34,6 +32,7 @@ K = {
     'conn.noisy': 24, 'cos.loss': 2, 'cos.dx': 64,
 }
 RATIOS = {}             # largest |kernel - float64| / (2^-24 S) seen per quantity (the margin each K leaves)
+within = checker(K, RATIOS)
 
 
 def gen(seed):
@@ -48,51 +47,6 @@ def stream():
 def L():
     from genrl_amd._lib import lib
     return lib()
-
-
-def within(what, got, ref, scale, key=None):
-    """|got - ref| <= K[key] 2^-24 scale elementwise (got: any device / dtype; ref, scale: float64 CPU)"""
-    key = key or what.split('[')[0]
-    got = got.detach().cpu().double()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    err = (got - ref).abs()
-    ratio = err / (U * scale).clamp_min(1e-300)
-    worst = float(torch.nan_to_num(ratio, nan=math.inf).max()) if ratio.numel() else 0.0
-    RATIOS[key] = max(RATIOS.get(key, 0.0), worst)
-    bad = ~(err <= K[key] * U * scale)
-    if bad.any():
-        i = tuple(int(v) for v in bad.nonzero()[0])
-        raise AssertionError(f'{what}: {int(bad.sum())} of {bad.numel()} elements out of bound (K = {K[key]}, worst ratio {worst:.3g}); '
-                             f'first at {i}: got {float(got[i])!r}, float64 {float(ref[i])!r}, scale {float(scale[i])!r}')
-
-
-def out_buf(rows, cols, ld, off=0):
-    """NaN-filled output [rows, cols] inside a buffer of rows + 1 lines of ld floats starting `off` floats in; the rest holds PAD"""
-    buf = torch.full(((rows + 1) * ld + off + 4,), PAD, device='cuda')
-    view = buf[off:off + rows * ld].view(rows, ld)[:, :cols]
-    view.fill_(float('nan'))
-    return buf, view
-
-
-def in_buf(src, ld, off=0):
-    """src (CPU fp32 [rows, cols]) copied into a device buffer of lines ld floats apart, `off` floats in; padding = NaN"""
-    rows, cols = src.shape
-    buf = torch.full(((rows + 1) * ld + off + 4,), float('nan'), device='cuda')
-    view = buf[off:off + rows * ld].view(rows, ld)[:, :cols]
-    view.copy_(src)
-    return view
-
-
-def untouched(what, buf, view):
-    """every float of buf outside `view` still holds PAD"""
-    mask = torch.ones_like(buf, dtype=torch.bool)
-    off = view.storage_offset() - buf.storage_offset()
-    rows, cols = view.shape if view.dim() == 2 else (1, view.numel())
-    ld = view.stride(0) if view.dim() == 2 else cols
-    idx = off + torch.arange(rows, device='cuda')[:, None] * ld + torch.arange(cols, device='cuda')[None, :]
-    mask[idx.reshape(-1)] = False
-    rest = buf[mask]
-    assert torch.equal(rest, torch.full_like(rest, PAD)), f'{what}: a kernel wrote outside its output'
 
 
 def vec_out(n):
