@@ -1323,7 +1323,7 @@ inline SplitPlan plan_split(int M, int N, int K) {
   SplitPlan p{tiles_b >= 512, 1, K};
   if (force) {
     p.big = force[0] == 'b';
-    const long s = atol(force + 2);
+    const long s = force[0] && force[1] == ',' ? atol(force + 2) : 1;   // ("m" alone: no count to read past its end)
     const int bk = p.big ? GENRL_BIG_BK : SMALL_BK;
     p.k_per_split = cdiv(cdiv(K, s > 0 ? s : 1), bk) * bk;
     p.splits = cdiv(K, p.k_per_split);
@@ -1583,7 +1583,6 @@ static int sgemm_impl(const float* A, long a_rs, long a_ks, const float* B, long
                       float* C, long ldc, const float* bias, int M, int N, int K,
                       int accumulate, float* ws, long ws_floats, void* stream, int G, const Gather* gp) {
   GENRL_ENTER();
-  g_last_pipe = 0;       // (the tall / skinny / fallback kernels run fp32 MFMAs; launch_rr overrides)
   if (M <= 0 || N <= 0) return GENRL_OK;
   if (K <= 0 || (a_rs != 1 && a_ks != 1) || (b_rs != 1 && b_ks != 1)) return GENRL_EINVAL;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1667,7 +1666,7 @@ static int sgemm_impl(const float* A, long a_rs, long a_ks, const float* B, long
       (rc = launch_rr<4>(A, a_rs, a_ks, B, b_rs, b_ks, C, ldc, bias, M, N, K, accumulate, p.splits, (p.k_per_split + 63) / 64 * 64,
                          wsp, s, G, gp)) >= 0)
     ;
-  else if (p.big)
+  else if (p.big && (trace_fallback(M, N, K, a_rs, a_ks, b_rs, b_ks, A, B), true))
     rc = launch_cfg<128, 128, GENRL_BIG_BK, GENRL_BIG_KG, GENRL_BIG_PD>(A, a_rs, a_ks, B, b_rs, b_ks, C, ldc, bias, M, N, K, accumulate,
                                                             p.splits, p.k_per_split, wsp, s, G, gp);
   else if (use_rr(M, N, K, p.splits) && (rc = launch_rr<2>(A, a_rs, a_ks, B, b_rs, b_ks, C, ldc, bias, M, N, K, accumulate, p.splits,
@@ -1699,9 +1698,12 @@ extern "C" int genrl_set_gemm_precision(int bf16 /* mode 0..3, see the header */
   return prev;
 }
 
+// g_last_pipe is reset here, not in sgemm_impl: a row-split product (tail_split_rows) runs sgemm_impl once per part and reports the
+// largest pipe of its launches (its main part), where a reset per part left the tail part's
 extern "C" int genrl_sgemm(const float* A, long a_rs, long a_ks, const float* B, long b_rs, long b_ks,
                            float* C, long ldc, const float* bias, int M, int N, int K,
                            int accumulate, float* ws, long ws_floats, void* stream) {
+  g_last_pipe = 0;       // (the tall / skinny / fallback kernels run fp32 MFMAs; launch_rr overrides)
   return sgemm_impl(A, a_rs, a_ks, B, b_rs, b_ks, C, ldc, bias, M, N, K, accumulate, ws, ws_floats, stream, 0, nullptr);
 }
 
@@ -1725,6 +1727,7 @@ extern "C" int genrl_sgemm_conv(const float* A, long a_rs, long a_ks, const floa
   // the patch-matrix side must have the logical shape (pixels x k*k*C)
   const long pixels = which == 1 ? M : K, kk = which == 1 ? K : N;
   if (kk != (long)ksize * ksize * img_c || pixels % g.ohw != 0) return GENRL_EINVAL;
+  g_last_pipe = 0;
   return sgemm_impl(A, a_rs, a_ks, B, b_rs, b_ks, C, ldc, bias, M, N, K, accumulate, ws, ws_floats, stream, which, &g);
 }
 
