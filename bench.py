@@ -3,8 +3,13 @@
 (BASELINE.json metric; configs[1]: batch 32 x seq 32, full WM + 2x connector + imag-behaviour
 update with video_text_reward), one process per GPU.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
+
+A plain run does what the headline needs and no more: set-up (hipGraph capture), the W warm-up and K timed steps, --dump-outputs,
+the line.  --full adds the measurements beside it (one GPU only): the eager leg, the fp32-MFMA comparison, the per-GEMM kernel
+roofline with its rocprofv3 PMC traffic passes, and the CPU baseline; --no-eager-leg / --no-fp32-mode / --no-kernel-profile /
+--no-traffic / --no-cpu-baseline leave single ones out.
 
 A step = one train.py iteration (train.py:273-340): agent.update_wm (WM Adam step + connector step)
 + wm.update_additional_detached_modules (2nd connector step) + agent.update_imag_behavior
@@ -333,8 +338,7 @@ def write_outputs(d, arrays):
     print(f'[bench] --dump-outputs: {len(arrays)} arrays of the last timed step in {d}', file=sys.stderr)
 
 
-def main():
-    global _real_stdout
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=10)
@@ -344,12 +348,16 @@ def main():
                          "c4 = configs[3] (128x128 frames, five-layer convs), c5 = configs[4] (data-free imagination update, 256 rows)")
     ap.add_argument('--batch', type=int, default=0, help='global batch (sequences); default: the config\'s own')
     ap.add_argument('--length', type=int, default=0, help='sequence length; default: the config\'s own')
-    ap.add_argument('--no-eager-leg', action='store_true', help='skip the short eager (no hipGraph) timing beside the replayed one')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-kernel-profile', action='store_true')
-    ap.add_argument('--no-fp32-mode', action='store_true', help='skip the comparison run with fp32 MFMAs throughout')
-    ap.add_argument('--no-traffic', action='store_true', help='skip the two rocprofv3 PMC passes (HBM bytes per GEMM launch)')
-    ap.add_argument('--dump-gemm', default='')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure what the headline does not need (one GPU): the eager leg, the fp32-MFMA '
+                         'comparison, the per-GEMM kernel roofline with its PMC traffic passes and the CPU baseline; a plain run leaves '
+                         'their fields null')
+    ap.add_argument('--no-eager-leg', action='store_true', help='--full: skip the short eager (no hipGraph) timing beside the replayed one')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-kernel-profile', action='store_true', help='--full: skip the per-GEMM kernel roofline (and the PMC passes)')
+    ap.add_argument('--no-fp32-mode', action='store_true', help='--full: skip the comparison run with fp32 MFMAs throughout')
+    ap.add_argument('--no-traffic', action='store_true', help='--full: skip the two rocprofv3 PMC passes (HBM bytes per GEMM launch)')
+    ap.add_argument('--dump-gemm', default='', metavar='FILE', help='--full: write the kernel profile\'s GEMM shapes and times as JSON')
     ap.add_argument('--dump-outputs', default='', metavar='DIR',
                     help='after the timed steps, write what the last one computed (its metrics and the trained weights, a fixed '
                          'sample of the larger tensors) as DIR/<name>.npy')
@@ -366,9 +374,19 @@ def main():
     ap.add_argument('--dp-graph', default='auto', choices=['auto', 'cut'],
                     help='data parallel: auto = collectives captured inside the graph when the backend is RCCL (falls back to '
                          'cuts, then eager); cut = collectives eager between graph segments')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    if not args.full:
+        if args.dump_gemm:
+            ap.error('--dump-gemm needs --full (the kernel profile writes it)')
+        args.no_eager_leg = args.no_fp32_mode = args.no_kernel_profile = args.no_traffic = args.no_cpu_baseline = True
+    return args
+
+
+def main():
+    global _real_stdout
+    args = parse_args()
     global PEAK_F32_MFMA_TFLOPS
     if args.precision == 16:
         PEAK_F32_MFMA_TFLOPS = PEAK_BF16_MFMA_TFLOPS   # the roofline of the bf16 mode is priced against the bf16 peak

@@ -38,4 +38,4 @@ timeout 200 python scripts/planes_bench.py > $O/planes_bench.txt 2>&1
 # (7) in-step time of the plane GEMM per shape; PMC passes; the full default bench line
 timeout 300 bash scripts/inshape.sh > $O/inshape.txt 2>&1
 timeout 600 bash scripts/pmc.sh > $O/pmc.txt 2>&1; cp gpurun_out/pmc/pmc_summary.json $O/pmc.json 2>/dev/null
-timeout 900 python bench.py > $O/bench_full.json 2> $O/bench_full.err
+timeout 900 python bench.py --full > $O/bench_full.json 2> $O/bench_full.err

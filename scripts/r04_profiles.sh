@@ -22,8 +22,8 @@ for b in 32 16 8 4; do
   echo "B=$b overlap on: $($B --batch $b --steps 30 2>/dev/null | ms)   no-overlap: $($B --batch $b --steps 30 --no-overlap 2>/dev/null | ms)"
 done > $O/batch_table.txt 2>&1
 # (4) one bench line per BASELINE config (graph replay + eager leg + per-pipe roofline; no PMC traffic passes except c2 and c4)
-for c in c3 c5; do timeout 600 python bench.py --config $c --no-cpu-baseline --no-traffic > $O/bench_$c.json 2> $O/bench_$c.err; done
-timeout 900 python bench.py --config c4 --no-cpu-baseline > $O/bench_c4.json 2> $O/bench_c4.err
+for c in c3 c5; do timeout 600 python bench.py --full --config $c --no-cpu-baseline --no-traffic > $O/bench_$c.json 2> $O/bench_$c.err; done
+timeout 900 python bench.py --full --config c4 --no-cpu-baseline > $O/bench_c4.json 2> $O/bench_c4.err
 # (5) per-phase kernels of one eager single-stream step
 timeout 300 bash scripts/phase_prof.sh 32 14 > $O/phase_b32.txt 2>&1
 timeout 300 bash scripts/phase_prof.sh 4 14 > $O/phase_b4.txt 2>&1
@@ -35,4 +35,4 @@ timeout 200 python scripts/convt_direct_time.py > $O/convt_direct_time.txt 2>&1
 # (7) in-step time of the plane GEMM per shape; PMC passes; the full default bench line (with CPU baseline and traffic)
 timeout 300 bash scripts/inshape.sh > $O/inshape.txt 2>&1
 timeout 600 bash scripts/pmc.sh > $O/pmc.txt 2>&1; cp gpurun_out/pmc/pmc_summary.json $O/pmc.json 2>/dev/null
-timeout 900 python bench.py > $O/bench_full.json 2> $O/bench_full.err
+timeout 900 python bench.py --full > $O/bench_full.json 2> $O/bench_full.err

@@ -10,4 +10,5 @@ bash scripts/ab.sh "GENRL_SUBPIXEL=0" "GENRL_SUBPIXEL=1" 2>&1 | tee gpurun_out/r
 bash scripts/ab.sh "GENRL_SUBPIXEL=1" "GENRL_SUBPIXEL=1 GENRL_SUBPIXEL_ODD=1" 2>&1 | tee -a gpurun_out/r04/ab_subpixel.txt
 python bench.py --config c4 --steps 10 --no-cpu-baseline --no-traffic --no-fp32-mode --no-eager-leg 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('c4', d['ms_per_step'])" | tee -a gpurun_out/r04/ab_subpixel.txt
 GENRL_SUBPIXEL=0 python bench.py --config c4 --steps 10 --no-cpu-baseline --no-traffic --no-fp32-mode --no-eager-leg 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('c4 subpixel off', d['ms_per_step'])" | tee -a gpurun_out/r04/ab_subpixel.txt
-python bench.py --steps 10 --no-cpu-baseline --no-traffic --no-fp32-mode --no-eager-leg --dump-gemm gpurun_out/r04/gemm_shapes.json > gpurun_out/r04/bench_sp.json 2>/dev/null
+O=${BENCH_OUT:-bench_out}/r04; mkdir -p $O
+python bench.py --full --steps 10 --no-cpu-baseline --no-traffic --no-fp32-mode --no-eager-leg --dump-gemm $O/gemm_shapes.json > $O/bench_sp.json 2>/dev/null

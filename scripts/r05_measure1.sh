@@ -19,5 +19,5 @@ echo "default (fp32 operands at 256 rows):   $($B --config c5 --steps 50 --warmu
 echo "GENRL_PLANES_MIN_ROWS=256 (planes):    $(GENRL_PLANES_MIN_ROWS=256 $B --config c5 --steps 50 --warmup 10 2>/dev/null | ms)"
 done
 } > $O/batch_table_c5.txt 2>&1
-for c in c3 c5; do timeout 900 python bench.py --config $c --no-cpu-baseline > $O/bench_$c.json 2> $O/bench_$c.err; done
+for c in c3 c5; do timeout 900 python bench.py --full --config $c --no-cpu-baseline > $O/bench_$c.json 2> $O/bench_$c.err; done
 cat $O/batch_table_c3.txt $O/batch_table_c5.txt

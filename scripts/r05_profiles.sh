@@ -51,7 +51,7 @@ echo "GENRL_PLANES_MIN_ROWS=256 (planes):    $(GENRL_PLANES_MIN_ROWS=256 $B --co
 done
 } > $O/batch_table_c5.txt 2>&1
 # (4) one bench line per BASELINE config (graph replay + eager leg + per-pipe roofline + PMC traffic with the per-kernel table)
-for c in c3 c4 c5; do timeout 900 python bench.py --config $c --no-cpu-baseline > $O/bench_$c.json 2> $O/bench_$c.err; done
+for c in c3 c4 c5; do timeout 900 python bench.py --full --config $c --no-cpu-baseline > $O/bench_$c.json 2> $O/bench_$c.err; done
 # (5) per-phase kernels of one eager single-stream step
 timeout 300 bash scripts/phase_prof.sh 32 14 > $O/phase_b32.txt 2>&1
 timeout 300 bash scripts/phase_prof.sh 4 14 > $O/phase_b4.txt 2>&1
@@ -62,5 +62,5 @@ rm -rf /tmp/k3; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/k3 
 python scripts/kernel_table.py /tmp/k3/p_kernel_trace.csv 4 3 > $O/kernel_table_c3.txt 2>&1
 rm -rf /tmp/k4; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/k4 -o p -- $B --config c4 --steps 6 --warmup 3 > /dev/null 2>&1
 python scripts/kernel_table.py /tmp/k4/p_kernel_trace.csv 4 > $O/kernel_table_c4.txt 2>&1
-timeout 900 python bench.py > $O/bench_c2.json 2> $O/bench_c2.err
+timeout 900 python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err
 tail -3 $O/feature_ab.txt; python -c "import json; d=json.load(open('$O/bench_c2.json')); print(d['ms_per_step'], d['config']['eager_ms_per_step'])"

@@ -5,7 +5,7 @@ O=gpurun_out/r06a; mkdir -p $O
 B="python bench.py --no-fp32-mode --no-kernel-profile --no-cpu-baseline --no-traffic --no-eager-leg"
 ms() { python -c "import json,sys; print(round(json.loads(sys.stdin.read())['ms_per_step'], 2))"; }
 timeout 900 python -m pytest tests/test_gpu_fullsize.py tests/test_gpu_planes.py tests/test_gpu_conv_planes.py -m gpu -x -q --timeout 250 -p no:cacheprovider > $O/tests.log 2>&1; echo "tests rc=$?"; tail -3 $O/tests.log
-timeout 600 python bench.py --no-cpu-baseline --no-traffic > $O/bench_c2.json 2> $O/bench_c2.err; python -c "
+timeout 600 python bench.py --full --no-cpu-baseline --no-traffic > $O/bench_c2.json 2> $O/bench_c2.err; python -c "
 import json; d=json.load(open('$O/bench_c2.json')); print(d['ms_per_step'], d['config']['eager_ms_per_step'], d['step_roofline'], d['roofline']['dominant_kernel'], d['roofline']['all_gemm'])"
 {
 for r in 1 2; do

@@ -34,7 +34,7 @@ for b in 64 32 16 8; do
 done
 } > $O/batch_table_c3.txt 2>&1
 # (4) one bench line per BASELINE config (graph replay + eager leg + per-pipe roofline + PMC traffic with the per-kernel table)
-for c in c3 c4 c5; do timeout 900 python bench.py --config $c --no-cpu-baseline > $O/bench_$c.json 2> $O/bench_$c.err; done
+for c in c3 c4 c5; do timeout 900 python bench.py --full --config $c --no-cpu-baseline > $O/bench_$c.json 2> $O/bench_$c.err; done
 # (5) in-step time of the plane GEMM per shape; PMC passes; kernel tables of c3 / c4 / c5; the full default bench line (CPU baseline, traffic)
 timeout 300 bash scripts/inshape.sh > $O/inshape.txt 2>&1
 timeout 600 bash scripts/pmc.sh > $O/pmc.txt 2>&1; cp gpurun_out/pmc/pmc_summary.json $O/pmc.json 2>/dev/null
@@ -42,5 +42,5 @@ for c in c3 c4 c5; do
 rm -rf /tmp/kc; timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kc -o p -- python bench.py --no-fp32-mode --no-kernel-profile --no-cpu-baseline --no-traffic --no-eager-leg --config $c --steps 6 --warmup 3 > /dev/null 2>&1
 python scripts/kernel_table.py /tmp/kc/p_kernel_trace.csv 4 $([ $c = c3 ] && echo 3) > $O/kernel_table_$c.txt 2>&1
 done
-timeout 900 python bench.py > $O/bench_c2.json 2> $O/bench_c2.err
+timeout 900 python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err
 cat $O/feature_ab.txt; python -c "import json; d=json.load(open('$O/bench_c2.json')); print(d['ms_per_step'], d['config']['eager_ms_per_step'], d['roofline']['dominant_kernel']['name'], d['roofline']['dominant_kernel']['frac'])"
