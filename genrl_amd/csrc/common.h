@@ -39,10 +39,12 @@ struct PlaneOut {           // optional plane output of a row kernel; p == nullp
 typedef _Float16 h2_f16x2 __attribute__((ext_vector_type(2)));
 typedef float h2_f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned h2_u32x2 __attribute__((ext_vector_type(2)));
-// 1 / s for a row whose largest magnitude is amax: s = 2^e puts amax * s into [2^14, 2^15) (fp16 tops out at 65504)
+// 1 / s for a row whose largest magnitude is amax: s = 2^e puts amax * s into [2^14, 2^15) (fp16 tops out at 65504).  s is capped
+// at 2^122 for a nonzero row (amax < 2^-108: its scaled values stay below 2^14); 2^-123 is left to the all-zero row alone, which the
+// two-segment products recognise by it (gemm_planes.hip, fold)
 __device__ __forceinline__ float h2_inv_of(float amax) {                    // amax >= 0 (or NaN / Inf)
   const int E = (int)((__builtin_bit_cast(unsigned, amax) >> 23) & 255u);
-  const int es = min(max(268 - E, 4), 250);                                 // exponent field of s
+  const int es = amax == 0.f ? 250 : min(max(268 - E, 4), 249);             // exponent field of s
   return __builtin_bit_cast(float, (unsigned)(254 - es) << 23);
 }
 __device__ __forceinline__ float h2_scale_of(float inv) {                   // 1 / inv for the powers of two above

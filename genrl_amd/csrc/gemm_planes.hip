@@ -113,6 +113,8 @@ __device__ __forceinline__ float pow2_ratio(float a, float b) {
   const int e = min(max(ea - eb + 127, 1), 254);
   return __builtin_bit_cast(float, (unsigned)e << 23);
 }
+// the inverse scale h2_inv_of gives an all-zero row, and only such a row (2^-123)
+__device__ __forceinline__ bool zero_row_inv(float inv) { return __builtin_bit_cast(unsigned, inv) == (4u << 23); }
 
 #ifndef LNE_ABL
 #define LNE_ABL 0      /* ablations of the LayerNorm epilogue (scripts/gemm_ln_abl.sh): 1 no y / plane stores, 2 no wait for the peers' records, 3 no SiLU, 4 no pre-activation store */
@@ -137,6 +139,7 @@ __global__ __launch_bounds__(256, (TM * TN == 1 && NS == 2 && FMT == 1) ? 2 : 1)
                                                          int tiles_m, int tiles_n, int xcd_m, SampleEpi smp, ConvGather cg, LnEpi ln) {
   static_assert(!LNE || (TM * TN == 1 && FMT == 1 && !CONV && PF == 0), "LayerNorm epilogue: 64x64 h2 tile");
   constexpr int BM = 64 * TM, BN = 64 * TN;
+  static_assert(!(FMT == 1 && FOLD) || (BM == 64 && BN == 64), "segment fold: 64x64 h2 tile");
   constexpr int NPL = FMT ? 2 : 3, NPROD = FMT ? 3 : 6;
   constexpr int ROWB = BK * 2;                         // bytes per tile row per plane
   constexpr int CPR = ROWB / 16;                       // 16-byte chunks per row (8 or 4)
@@ -414,20 +417,43 @@ __global__ __launch_bounds__(256, (TM * TN == 1 && NS == 2 && FMT == 1) ? 2 : 1)
 
   // h2, two segments: the operands of segment 1 carry other row scales than those of segment 0 -- when the MFMA stream
   // crosses the boundary the accumulators are multiplied by (scale of segment 0) / (scale of segment 1), an exact power of
-  // two per element, and the epilogue undoes the scaling of the last segment only
+  // two per element, and the epilogue undoes the scaling of the last segment only.  A segment-1 row (column) whose inverse scale
+  // is 2^-123 -- h2_inv_of gives it to all-zero rows only: a zero state, a zero-initialised weight slice -- adds nothing, but its
+  // ratio (2^109 next to a row of magnitude ~1) would carry the segment-0 sums out of fp32's range (Inf): such a row keeps the scale
+  // of segment 0 instead: its factor in the LDS copy the epilogue reads becomes segment 0's (below, behind the prologue's barrier;
+  // fold() and the epilogue read it behind the K loop's barriers), so that its ratio is 1.  (Limit: a NONZERO segment-1 row about
+  // 2^90 or more below its segment-0 row still overflows, as it did before.)
+  if constexpr (FMT == 1 && FOLD) {
+    // (behind the prologue's barrier: the DMA-ed factors of segment 1 are in LDS) wave 0: the tile's rows, wave 1: its columns; only
+    // a zero row reads global memory
+    if (s1.k && wave < 2) {
+      typedef __attribute__((address_space(3))) float lds_f32;
+      lds_f32* const f = reinterpret_cast<lds_f32*>((uintptr_t)(lds0 + EPI_AT + 4 * (wave * BM + lane)));
+      if ((wave ? s1.b_inv : s1.a_inv) && zero_row_inv(*f)) {
+        const float* const inv0 = wave ? s0.b_inv : s0.a_inv;
+        *f = inv0 ? inv0[min((wave ? n0 : m0) + lane, (wave ? N : M) - 1)] : 1.f;
+      }
+    }
+  }
+  // (the factors of segment 1 come from that LDS copy: a zero row's ratio is 1 there)
+  auto epi1 = [&](int i) __attribute__((always_inline)) -> float {
+    return *reinterpret_cast<const __attribute__((address_space(3))) float*>((uintptr_t)(lds0 + EPI_AT + 4 * i));
+  };
   int it = 0;                          // stage whose MFMAs are issued next
   auto fold = [&]() __attribute__((always_inline)) {
     if constexpr (FMT == 1) {
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         const int row = min(m0 + (wm * TM + i) * 32 + l32, M - 1);
-        const float rf = (s0.a_inv && s1.a_inv) ? pow2_ratio(s0.a_inv[row], s1.a_inv[row]) : (s0.a_inv ? s0.a_inv[row] : (s1.a_inv ? pow2_ratio(1.f, s1.a_inv[row]) : 1.f));
+        const int ri = (wm * TM + i) * 32 + l32;
+        const float rf = (s0.a_inv && s1.a_inv) ? pow2_ratio(s0.a_inv[row], epi1(ri)) : (s0.a_inv ? s0.a_inv[row] : (s1.a_inv ? pow2_ratio(1.f, epi1(ri)) : 1.f));
 #pragma unroll
         for (int j = 0; j < TN; ++j)
 #pragma unroll
           for (int v = 0; v < 16; ++v) {
             const int col = min(n0 + (wn * TN + j) * 32 + 8 * (v / 4) + 4 * h32 + v % 4, N - 1);
-            const float cf = (s0.b_inv && s1.b_inv) ? pow2_ratio(s0.b_inv[col], s1.b_inv[col]) : (s0.b_inv ? s0.b_inv[col] : (s1.b_inv ? pow2_ratio(1.f, s1.b_inv[col]) : 1.f));
+            const int ci = BM + (wn * TN + j) * 32 + 8 * (v / 4) + 4 * h32 + v % 4;
+            const float cf = (s0.b_inv && s1.b_inv) ? pow2_ratio(s0.b_inv[col], epi1(ci)) : (s0.b_inv ? s0.b_inv[col] : (s1.b_inv ? pow2_ratio(1.f, epi1(ci)) : 1.f));
 #pragma unroll
             for (int c = 0; c < NACC; ++c) acc[c][i][j][v] *= rf * cf;
           }
@@ -1641,6 +1667,12 @@ int g_planes_force_tile = 0;     // 0 auto, 1: 64x64, 2: 128x128 (experiments)
 
 }  // namespace
 
+// genrl_planes_last_route: the instantiations (GENRL_ROUTE_* bits, include/genrl_hip.h) the last plane entry call launched
+unsigned g_planes_route = 0;
+int g_planes_route_splits = 0;
+static inline void route_reset() { g_planes_route = 0; g_planes_route_splits = 0; }
+static inline void route(unsigned bit) { g_planes_route |= bit; }
+
 extern "C" {
 
 void genrl_log_launch(const char* family, long M, long N, long K, double operand_bytes) {
@@ -1650,6 +1682,7 @@ void genrl_log_launch(const char* family, long M, long N, long K, double operand
 
 int genrl_planes_force_tile(int t) { const int p = g_planes_force_tile; g_planes_force_tile = t; return p; }
 int genrl_planes_variant(int v) { const int p = g_planes_variant; g_planes_variant = v; return p; }
+long genrl_planes_last_route(void) { return (long)g_planes_route | ((long)g_planes_route_splits << 32); }
 
 /* x (R x Cn fp32, row stride ldx) -> three bf16 planes [R][ld_out] (or [Cn][ld_out] when transpose), zero padded */
 int genrl_split_x3(const float* x, long ldx, int R, int Cn, uint16_t* out, long ld_out, long plane, int transpose,
@@ -1679,6 +1712,7 @@ int genrl_gemm_x3(const uint16_t* a0, long a0_ld, long a0_plane, const uint16_t*
                   const uint16_t* a1, long a1_ld, long a1_plane, const uint16_t* b1, long b1_ld, long b1_plane, int k1,
                   float* C, long ldc, const float* bias, int M, int N, int accumulate, void* stream) {
   GENRL_ENTER();
+  route_reset();
   if (M <= 0 || N <= 0 || k0 <= 0 || (k0 & 63) || (k1 & 63) || k1 < 0) return GENRL_EINVAL;
   if ((a0_ld & 7) || (b0_ld & 7) || (k1 && ((a1_ld & 7) || (b1_ld & 7)))) return GENRL_EINVAL;
   PlaneSeg s0{a0, a0_ld, a0_plane, b0, b0_ld, b0_plane, k0, nullptr, nullptr}, s1{a1, a1_ld, a1_plane, b1, b1_ld, b1_plane, k1, nullptr, nullptr};
@@ -1687,11 +1721,13 @@ int genrl_gemm_x3(const uint16_t* a0, long a0_ld, long a0_plane, const uint16_t*
   if (big) {
     const int tm = cdiv(M, 128), tn = cdiv(N, 128);
     log_launch("x3/128", M, N, k0 + k1, 6.0 * ((double)M + N) * (k0 + k1) + 4.0 * M * N);
+    route(GENRL_ROUTE_X3_128);
     gemm_planes_kernel<2, 2, 32, 1, 0, 3><<<tm * tn, 256, 0, (hipStream_t)stream>>>(s0, s1, C, ldc, bias, M, N, accumulate, tm, tn,
                                                                                 xcd_split(tm, tn), SampleEpi{}, ConvGather{}, LnEpi{});
   } else {
     const int tm = cdiv(M, 64), tn = cdiv(N, 64);
     log_launch("x3/64", M, N, k0 + k1, 6.0 * ((double)M + N) * (k0 + k1) + 4.0 * M * N);
+    route(GENRL_ROUTE_X3_64);
     gemm_planes_kernel<1, 1, 64, 3, 0, 3><<<tm * tn, 256, 0, (hipStream_t)stream>>>(s0, s1, C, ldc, bias, M, N, accumulate, tm, tn,
                                                                                 xcd_split(tm, tn), SampleEpi{}, ConvGather{}, LnEpi{});
   }
@@ -1793,6 +1829,7 @@ static int gemm_h2_impl(const uint16_t* a0, long a0_ld, long a0_plane, const flo
       const float* bs = seg ? nullptr : bias;
       const int acc = seg ? 1 : accumulate;
       log_launch("h2/128", M, N, sg.k, kk_bytes(M, N, sg.k));
+      route(!hl_on() ? GENRL_ROUTE_128_PLAIN : use_wide(N) ? GENRL_ROUTE_128_HLW : GENRL_ROUTE_128_HL);      // (the default chain's kernel; the experiments' variants report it too)
 #ifdef PLANES_EXPERIMENTS
       if (g_planes_variant == 1 || g_planes_variant == 6)
         gemm_planes_kernel<2, 2, 64, 2, 1, 2, false, false, 2><<<tm * tn, 256, 0, (hipStream_t)stream>>>(sg, none, C, ldc, bs, M, N, acc, tm, tn,
@@ -1837,6 +1874,7 @@ static int gemm_h2_impl(const uint16_t* a0, long a0_ld, long a0_plane, const flo
     // 25.8 -> 20.2; 1200 tiles K 1024 58 -> 53; but 256 tiles 11.2 -> 13.8 and 768 tiles at K 2048 62 -> 64 (the two-stage ring is too
     // shallow for long K loops on its own): from 257 tiles up while K <= 1536
     const bool two = two_env ? two_env[0] == '1' : (ntile > 256 && k0 + k1 <= 1536);
+    route(smp.q ? GENRL_ROUTE_64_SAMPLE : (two ? GENRL_ROUTE_64_NS2 : GENRL_ROUTE_64_NS3));
     if (two && !smp.q) L64(2, 0);
     else L64(3, 0);
 #endif
@@ -1853,6 +1891,7 @@ int genrl_gemm_h2_conv(const uint16_t* img, long ld_img, long plane_img, const f
                        const uint16_t* b, long b_ld, long b_plane, const float* b_inv, float* C, long ldc, const float* bias, int N,
                        int accumulate, void* stream) {
   GENRL_ENTER();
+  route_reset();
   const int Ho = (H - k) / 2 + 1, Wo = (W - k) / 2 + 1, K = k * k * Cc;
   const long Ml = (long)Nimg * Ho * Wo;
   /* (K >= 64: every chunk of the first stage lies inside the patch -- the gather's run-off rule only covers LATER stages) */
@@ -1867,6 +1906,7 @@ int genrl_gemm_h2_conv(const uint16_t* img, long ld_img, long plane_img, const f
   const bool tall = hl_on() && use_tall96(N, K);      // N <= 96 (the 48 -> 96 channel layer): 256 x 96 tiles instead of 128 x 128 with a quarter padding
   const int tm = cdiv(M, tall ? 256 : 128), tn = tall ? 1 : cdiv(N, wide ? 192 : 128);
   log_launch("h2/conv128", M, N, (int)b_ld, 4.0 * ((double)Nimg * H * W * Cc + (double)N * b_ld + (double)M * N));
+  route(tall ? GENRL_ROUTE_CONV_TALL96 : wide ? GENRL_ROUTE_CONV_HLW : hl_on() ? GENRL_ROUTE_CONV_HL : GENRL_ROUTE_CONV_PLAIN);
   if (tall)
     gemm_planes_hlw_kernel<true, 3, 4><<<tm * tn, 256, 0, (hipStream_t)stream>>>(s0, C, ldc, bias, M, N, accumulate, tm, tn, xcd_split(tm, tn),
                                                                                 ConvGather{H, W, Cc, k, Ho, Wo, K, 2, 0, 0, 0});
@@ -1896,6 +1936,7 @@ int genrl_gemm_h2_subpixel(const uint16_t* img, long ld_img, long plane_img, con
                            const uint16_t* b, long b_ld, long b_plane, const float* b_inv, float* out, int Ho, int Wo, int Co,
                            const float* bias, void* stream) {
   GENRL_ENTER();
+  route_reset();
   const int Hq = Hp - T + 1, Wq = Wp - T + 1, K = T * T * Cc, N = 4 * Co;
   const long Ml = (long)Nimg * Hq * Wq;
   if (Nimg <= 0 || T < 1 || Hq <= 0 || Wq <= 0 || Co <= 0 || (Co & 3) || (Cc & 7) || Cc < 48 || ld_img < Cc || (ld_img & 7) || (b_ld & 63) ||
@@ -1909,6 +1950,7 @@ int genrl_gemm_h2_subpixel(const uint16_t* img, long ld_img, long plane_img, con
   const bool wide = use_wide(N);
   const int tm = cdiv(M, 128), tn = cdiv(N, wide ? 192 : 128);
   log_launch("h2/subpixel128", M, N, (int)b_ld, 4.0 * ((double)Nimg * Hp * Wp * Cc + (double)N * b_ld + (double)Nimg * Ho * Wo * Co));
+  route(wide ? GENRL_ROUTE_SUBPIXEL_HLW : GENRL_ROUTE_SUBPIXEL_HL);
   if (wide)
     gemm_planes_hlw_kernel<true, 3><<<tm * tn, 256, 0, (hipStream_t)stream>>>(s0, out, 4, bias, M, N, 0, tm, tn, xcd_split(tm, tn),
                                                                              ConvGather{Hp, Wp, Cc, T, Hq, Wq, K, 1, Ho, Wo, Co});
@@ -1923,6 +1965,7 @@ int genrl_gemm_h2(const uint16_t* a0, long a0_ld, long a0_plane, const float* a0
                   const float* b0_inv, int k0, const uint16_t* a1, long a1_ld, long a1_plane, const float* a1_inv,
                   const uint16_t* b1, long b1_ld, long b1_plane, const float* b1_inv, int k1,
                   float* C, long ldc, const float* bias, int M, int N, int accumulate, void* stream) {
+  route_reset();
   return gemm_h2_impl(a0, a0_ld, a0_plane, a0_inv, b0, b0_ld, b0_plane, b0_inv, k0, a1, a1_ld, a1_plane, a1_inv, b1, b1_ld, b1_plane,
                       b1_inv, k1, C, ldc, bias, M, N, accumulate, stream, SampleEpi{});
 }
@@ -1953,6 +1996,7 @@ int genrl_gemm_h2_ln(const uint16_t* a0, long a0_ld, long a0_plane, const float*
                      float* y, long ldy, float* mean, float* rstd, uint16_t* yp, long yld, long yplane, float* yinv,
                      float* part, unsigned* sync, void* stream) {
   GENRL_ENTER();
+  route_reset();
   if (!genrl_gemm_h2_ln_ok(M, N) || k0 <= 0 || (k0 & 63) || (k1 & 63) || k1 < 0 || !gamma || !beta || !part || !sync || !C) return GENRL_EINVAL;
   if ((a0_ld & 7) || (b0_ld & 7) || (k1 && ((a1_ld & 7) || (b1_ld & 7))) || (ldc & 3) || (y && (ldy & 3)) || (yp && ((yld & 3) || !yinv))) return GENRL_EINVAL;
   if (((reinterpret_cast<uintptr_t>(C) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta) |
@@ -1962,6 +2006,7 @@ int genrl_gemm_h2_ln(const uint16_t* a0, long a0_ld, long a0_plane, const float*
   const int tm = cdiv(M, 64), tn = N / 64;
   const LnEpi ln{gamma, beta, eps, act, y, ldy, yp, yld, yplane, yinv, mean, rstd, part, sync};
   log_launch("h2/64ln", M, N, k0 + k1, kk_bytes(M, N, k0 + k1));
+  route(GENRL_ROUTE_64_LN);
   gemm_planes_kernel<1, 1, 64, 3, 1, 3, true, false, 0, true><<<8 * cdiv(tm, 8) * tn, 256, 0, (hipStream_t)stream>>>(
       s0, s1, C, ldc, bias, M, N, 0, tm, tn, 0, SampleEpi{}, ConvGather{}, ln);
   GENRL_CHECK_LAUNCH();
@@ -1976,6 +2021,7 @@ int genrl_gemm_h2_sample(const uint16_t* a0, long a0_ld, long a0_plane, const fl
                          long b0_plane, const float* b0_inv, int k0, float* C, long ldc, const float* bias, int M, int N,
                          const float* q, long ldq, float unimix, float* sample, long lds, uint16_t* sp, long sld, long splane,
                          float* sinv, void* stream) {
+  route_reset();
   if (!q || !sample || (N & 31) || (ldc & 3) || (ldq & 3) || (lds & 3) || (sp && ((sld & 3) || !sinv))) return GENRL_EINVAL;
   if (((reinterpret_cast<uintptr_t>(C) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(q) |
         reinterpret_cast<uintptr_t>(sample)) & 15) != 0 || (reinterpret_cast<uintptr_t>(sp) & 7) != 0)

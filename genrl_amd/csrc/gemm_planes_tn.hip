@@ -489,6 +489,9 @@ TnPlan tn_plan(int NI, int NJ, int M) {
 
 }  // namespace
 
+extern unsigned g_planes_route;        // (gemm_planes.hip: genrl_planes_last_route)
+extern int g_planes_route_splits;
+
 extern "C" {
 
 /* bytes of workspace genrl_gemm_h2_tn needs: factors (fp16, M + 128), per-split cref, split-K partial tiles */
@@ -516,6 +519,8 @@ static int tn_impl(const uint16_t* a, long a_ld, long a_plane, const float* a_in
   const TnPlan pl = tn_plan(NI, NJ, M);
   const int nsplit = pl.nsplit, sps = pl.sps;
   if (nsplit > 1 && ((NJ & 3) || (ldc & 3))) return GENRL_EINVAL;     // (the callers' weight matrices: multiples of 4 columns)
+  g_planes_route = rowoff ? GENRL_ROUTE_TN_CONV : GENRL_ROUTE_TN;
+  g_planes_route_splits = nsplit;
   char* w = reinterpret_cast<char*>(ws);
   u16* fac = reinterpret_cast<u16*>(w);
   float* cref = reinterpret_cast<float*>(w + pl.fac_bytes);
@@ -549,6 +554,7 @@ static int tn_impl(const uint16_t* a, long a_ld, long a_plane, const float* a_in
 int genrl_gemm_h2_tn(const uint16_t* a, long a_ld, long a_plane, const float* a_inv, const uint16_t* b, long b_ld, long b_plane,
                      const float* b_inv, float* C, long ldc, int NI, int NJ, int M, int accumulate, void* ws, long ws_bytes,
                      void* stream) {
+  g_planes_route = 0; g_planes_route_splits = 0;
   return tn_impl(a, a_ld, a_plane, a_inv, b, b_ld, b_plane, b_inv, C, ldc, NI, NJ, M, accumulate, ws, ws_bytes, nullptr, 0, 0, 0, stream);
 }
 
@@ -559,6 +565,7 @@ int genrl_gemm_h2_tn(const uint16_t* a, long a_ld, long a_plane, const float* a_
 int genrl_gemm_h2_tn_conv(const uint16_t* a, long a_ld, long a_plane, const float* a_inv, const uint16_t* img, long ld_img,
                           long plane_img, const float* img_inv, const unsigned* rowoff, int W, int Cc, int k, float* C, long ldc,
                           int NI, int M, int accumulate, void* ws, long ws_bytes, void* stream) {
+  g_planes_route = 0; g_planes_route_splits = 0;
   if (!rowoff || k <= 0) return GENRL_EINVAL;
   return tn_impl(a, a_ld, a_plane, a_inv, img, ld_img, plane_img, img_inv, C, ldc, NI, k * k * Cc, M, accumulate, ws, ws_bytes, rowoff,
                  W, Cc, k, stream);

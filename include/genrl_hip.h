@@ -345,6 +345,28 @@ int genrl_gemm_x3(const uint16_t* a0, long a0_ld, long a0_plane, const uint16_t*
                   float* C, long ldc, const float* bias, int M, int N, int accumulate, void* stream);
 int genrl_planes_force_tile(int t);      /* experiments: 0 auto, 1 64x64 tiles, 2 128x128 tiles (both formats) */
 int genrl_planes_variant(int v);         /* experiments: ring depth / L2 prefetch distance of the plane kernels (scripts/cold_bench.py) */
+/* kernel instantiations the most recent plane product entry call (genrl_gemm_h2, _sample, _ln, _conv, _subpixel, _tn, _tn_conv,
+ * genrl_gemm_x3) launched, reset by each such call (a refused call reports none): the GENRL_ROUTE_* bits OR-ed in the low 32 bits
+ * -- a row-split product or a two-segment 128-tile product reports both of its launches -- and the split-K count of a TN product
+ * in the high bits (tests: which route a product took; the launch-log families do not tell the kernels of a family apart) */
+long genrl_planes_last_route(void);
+#define GENRL_ROUTE_64_NS3        0x1u      /* 64x64 tile, three-stage ring */
+#define GENRL_ROUTE_64_NS2        0x2u      /* 64x64 tile, two-stage ring, two workgroups per CU */
+#define GENRL_ROUTE_64_SAMPLE     0x4u      /* 64x64 tile with the categorical-sample epilogue */
+#define GENRL_ROUTE_64_LN         0x8u      /* 64x64 tile with the LayerNorm epilogue */
+#define GENRL_ROUTE_128_PLAIN     0x10u     /* 128x128 tile, two whole stages (GENRL_PLANES_HL=0) */
+#define GENRL_ROUTE_128_HL        0x20u     /* 128x128 tile, plane-alternating half stages */
+#define GENRL_ROUTE_128_HLW       0x40u     /* 128x192 tile, half stages */
+#define GENRL_ROUTE_CONV_PLAIN    0x80u
+#define GENRL_ROUTE_CONV_HL       0x100u
+#define GENRL_ROUTE_CONV_HLW      0x200u
+#define GENRL_ROUTE_CONV_TALL96   0x400u    /* 256x96 tile */
+#define GENRL_ROUTE_SUBPIXEL_HL   0x800u
+#define GENRL_ROUTE_SUBPIXEL_HLW  0x1000u
+#define GENRL_ROUTE_X3_64         0x2000u
+#define GENRL_ROUTE_X3_128        0x4000u
+#define GENRL_ROUTE_TN            0x8000u
+#define GENRL_ROUTE_TN_CONV       0x10000u
 
 /* Row kernels with an additional h2-plane output (the operand of the next genrl_gemm_h2): same arithmetic and fp32
  * outputs as the entry points without the suffix (documented below), plus planes [.][ldp] `plane` elements apart and

@@ -1,4 +1,4 @@
-"""Helpers of the float64 kernel tests (test_gpu_row_kernel_variants.py, test_gpu_dist_optim_variants.py): per-element bounds
+"""Helpers of the float64 kernel tests (test_gpu_row_kernel_variants.py, test_gpu_dist_optim_variants.py, test_gpu_plane_variants.py): per-element bounds
 against a float64 reference, NaN-prefilled output buffers with padding columns and a guard row, and the check that a kernel
 wrote nothing outside its output."""
 import math
@@ -48,6 +48,11 @@ def in_buf(src, ld, off=0):
 
 def untouched(what, buf, view):
     """every float of buf outside `view` still holds PAD"""
+    assert untouched_ok(buf, view), f'{what}: a kernel wrote outside its output'
+
+
+def untouched_ok(buf, view):
+    """-> whether every float of buf outside `view` still holds PAD"""
     mask = torch.ones_like(buf, dtype=torch.bool)
     off = view.storage_offset() - buf.storage_offset()
     rows, cols = view.shape if view.dim() == 2 else (1, view.numel())
@@ -55,4 +60,4 @@ def untouched(what, buf, view):
     idx = off + torch.arange(rows, device='cuda')[:, None] * ld + torch.arange(cols, device='cuda')[None, :]
     mask[idx.reshape(-1)] = False
     rest = buf[mask]
-    assert torch.equal(rest, torch.full_like(rest, PAD)), f'{what}: a kernel wrote outside its output'
+    return bool(torch.equal(rest, torch.full_like(rest, PAD)))
