@@ -380,18 +380,12 @@ extern "C" int genrl_subpixel_weight(const float* W, long s_ci, long s_co, long 
 // consecutive patch positions (py, px0 .. px0 + 15) of one image: rows of a v_mfma_f32_16x16x4_f32 block; columns n = (a, b, c):
 // the four output parity classes x Co channels (12 of 16 used); K = T T Ci: the T x T input patch.  A lane's float4 at
 // x[image][py + u - (T-1)][px + v - (T-1)][16 j + 4 (lane / 16) ..] IS its A fragment for 4 MFMA steps (any k order works as long as
-// both operands use it), the weight fragments of all T T Ci / 4 steps live in registers for the whole kernel (108 VGPRs), so the
+// both operands use it), the weight fragments of all T T Ci / 4 steps are loaded once for the whole kernel (into LDS, below), so the
 // loop is: 3 predicated 16-byte loads + 12 MFMAs per tap, no LDS, no barrier.  Output NCHW (the reference's frame layout) or NHWC:
 // the block's 2 x Co x 32 (NCHW) outputs leave through a per-wave LDS transpose as 16-byte stores.  Exact fp32 arithmetic.
-#ifndef CONVT_ABL
-#define CONVT_ABL 0
-#endif
-#ifndef CONVT_FWD_WLDS
-#define CONVT_FWD_WLDS 1      /* the 3-channel forward kernel's weights in LDS (0: in 108 registers, round 4) */
-#endif
 namespace {
 template <int T, int J>      // k = 2T taps per dimension pair; Ci = 16 J
-__global__ __launch_bounds__(256, CONVT_FWD_WLDS ? 4 : 3) void convt_small_co_fwd_kernel(const float* __restrict__ x, const float* __restrict__ Wp,
+__global__ __launch_bounds__(256, 4) void convt_small_co_fwd_kernel(const float* __restrict__ x, const float* __restrict__ Wp,
                                                                  const float* __restrict__ bias, float* __restrict__ out, int Nimg,
                                                                  int Hi, int Wi, int Co, int out_nchw) {
   constexpr int Ci = 16 * J, NS = T * T * J * 4, k = 2 * T;
@@ -403,13 +397,9 @@ __global__ __launch_bounds__(256, CONVT_FWD_WLDS ? 4 : 3) void convt_small_co_fw
   const long nblk = (long)Nimg * Hq * bpr;
   // ---- weight fragments: step s = ((u T + v) J + j) 4 + e multiplies k = (u, v, ci = 16 j + 4 kq + e); this lane's column n = r
   const int n = r, cls = n / Co, c_n = n - cls * Co, a_n = cls >> 1, b_n = cls & 1;
-#if CONVT_FWD_WLDS
   // (round 5: the NS = 108 weight words per lane live in LDS -- one table for the four waves, a 16-byte conflict-free read per 4 MFMAs --
   // instead of 108 registers: more waves per SIMD to hide the tap loads behind)
   __shared__ float4 wl[NS / 4][64];
-#else
-  float bf[NS];
-#endif
 #pragma unroll
   for (int u = 0; u < T; ++u)
 #pragma unroll
@@ -420,16 +410,10 @@ __global__ __launch_bounds__(256, CONVT_FWD_WLDS ? 4 : 3) void convt_small_co_fw
         for (int e = 0; e < 4; ++e) {
           const int kh = a_n + 2 * (T - 1 - u), kw = b_n + 2 * (T - 1 - v), ci = 16 * j + 4 * kq + e;
           const int s = ((u * T + v) * J + j) * 4 + e;
-#if CONVT_FWD_WLDS
           if ((s / 4) % 4 == wave)
             reinterpret_cast<float*>(&wl[s / 4][lane])[e] = (n < 4 * Co) ? Wp[(long)ci * (k * k * Co) + (kh * k + kw) * Co + c_n] : 0.f;
-#else
-          bf[s] = (n < 4 * Co) ? Wp[(long)ci * (k * k * Co) + (kh * k + kw) * Co + c_n] : 0.f;
-#endif
         }
-#if CONVT_FWD_WLDS
   __syncthreads();
-#endif
   const float bias_n = (bias && n < 4 * Co) ? bias[c_n] : 0.f;
   // taps in flight: the loads of tap t + 1 are issued before the 4 J MFMAs of tap t (two register sets), and the loads of the NEXT block's
   // first tap before the last tap's MFMAs and this block's epilogue (they were exposed once per block: 9 taps of ~400 MFMA cycles each
@@ -468,34 +452,20 @@ __global__ __launch_bounds__(256, CONVT_FWD_WLDS ? 4 : 3) void convt_small_co_fw
     f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};     // (one chain: per-channel-group accumulators measured no faster, 229 vs 190 us)
 #pragma unroll
     for (int tap = 0; tap < T * T; ++tap) {
-#if CONVT_ABL != 2       /* ablation 2 (scripts/convt_abl.sh): no operand loads in the tap loop */
       if (tap + 1 < T * T) load_tap(bx, py, img, tap + 1, av[(tap + 1 + PAR) & 1]);
       else if (more) load_tap(nbx, npy, nimg, 0, av[(tap + 1 + PAR) & 1]);
-#endif
 #pragma unroll
       for (int j = 0; j < J; ++j) {
         const int s = (tap * J + j) * 4;
         const float4 a4 = av[(tap + PAR) & 1][j];
-#if CONVT_FWD_WLDS
         const float4 w4 = wl[s / 4][lane];
         const float bw[4] = {w4.x, w4.y, w4.z, w4.w};
-#else
-        const float* bw = bf + s;
-#endif
-#if CONVT_ABL == 1       /* ablation 1: no MFMAs (operands kept live) */
-        asm volatile("" ::"v"(a4.x), "v"(a4.y), "v"(a4.z), "v"(a4.w), "v"(bw[0]), "v"(bw[3]));
-#else
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.x, bw[0], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.y, bw[1], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.z, bw[2], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.w, bw[3], acc, 0, 0, 0);
-#endif
       }
     }
-#if CONVT_ABL == 3       /* ablation 3: no epilogue (LDS transpose + stores) */
-    asm volatile("" ::"v"(acc[0]), "v"(acc[3]));
-    return;
-#endif
     // D[i = 4 kq + vv][n = r]: patch position px0 + i, column (a, b, c) -> output pixel (2 py + a, 2 (px0 + i) + b), channel c
     if (n < 4 * Co) {
 #pragma unroll
@@ -549,7 +519,7 @@ extern "C" int genrl_convt_small_co_fwd(const float* x, const float* Wp, const f
     return GENRL_EINVAL;
   const long nblk = (long)Nimg * (Hi + 2) * ((Wi + 2 + 15) / 16);
   /* resident waves only (5 per SIMD with the weights in LDS: 678 us at 4 096 images against 727 with them in registers, 3 per SIMD) */
-  const int wg_cap = CONVT_FWD_WLDS ? 1280 : 768;
+  const int wg_cap = 1280;
   const int blocks = (int)(cdiv(nblk, 4) < wg_cap ? cdiv(nblk, 4) : wg_cap);
   hipLaunchKernelGGL((convt_small_co_fwd_kernel<3, 3>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, Wp, bias, out, Nimg, Hi, Wi, Co,
                      out_nchw);
@@ -567,7 +537,7 @@ namespace {
 // walked in GROUPS g = (c, kh, kw pair p): lane (r, kq) of round t takes group 4 t + kq and loads the float2 dy[c][2 iy + kh][2 ix + 2 p ..]
 // -- 8-byte loads that are CONTIGUOUS across the 16 pixels of the block (the first version's 4-byte loads at an 8-byte lane stride ran the
 // kernel at a fifth of the matrix rate) -- and the two floats are the A operands of two MFMA steps (kw = 2 p, 2 p + 1).
-// Round 5 (ablations: scripts/convt_abl.sh -- 704 us shipped at 4 096 images, 545 without the MFMAs, 395 without the dy loads, 420 without the
+// Round 5 (ablations, profiles/r05_convt_abl.txt: 704 us shipped at 4 096 images, 545 without the MFMAs, 395 without the dy loads, 420 without the
 // stores): the 84 weight words per lane moved from registers into LDS (16-byte reads, conflict-free: the same for all four waves), which
 // leaves room for the NEXT block's 14 loads to be in flight under this block's MFMAs and for more waves per SIMD, and the 16 x Ci output
 // block leaves through a per-wave LDS transpose as 16-byte stores of whole pixel rows instead of 4-byte stores in 64-byte segments.
@@ -702,43 +672,27 @@ __global__ __launch_bounds__(256) void convt_small_co_wgrad_kernel(const float* 
     const float* dp = dy + (long)img * Co * Ho * Wo + (long)(2 * iy) * Wo + 2 * (pv ? ix : 0);
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) {
-#if CONVT_ABL == 23
-      a[rb] = (float)(ix + rb);
-#else
       a[rb] = xp[16 * rb]; if (!pv) a[rb] = 0.f;
-#endif
     }
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {
-#if CONVT_ABL == 22
-      b[cb] = (float)(ix + cb);
-#else
       b[cb] = dp[boff[cb] >= 0 ? boff[cb] : 0]; if (!pv || boff[cb] < 0) b[cb] = 0.f;
-#endif
     }
   };
   float a0[RB], b0[NCB], a1[RB], b1[NCB];
   if (g0 < g1) load(g0, a0, b0);
   for (int g = g0; g < g1; g += 2) {
     if (g + 1 < g1) load(g + 1, a1, b1);
-#if CONVT_ABL == 21      /* ablations 21 / 22: wgrad without MFMAs / without the dy-patch loads / 23: without the x loads */
-    asm volatile("" ::"v"(a0[0]), "v"(a0[RB - 1]), "v"(b0[0]), "v"(b0[NCB - 1]));
-#else
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[rb], b0[cb], acc[rb][cb], 0, 0, 0);
-#endif
     if (g + 1 < g1) {
       if (g + 2 < g1) load(g + 2, a0, b0);
-#if CONVT_ABL == 21
-      asm volatile("" ::"v"(a1[0]), "v"(a1[RB - 1]), "v"(b1[0]), "v"(b1[NCB - 1]));
-#else
 #pragma unroll
       for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[rb], b1[cb], acc[rb][cb], 0, 0, 0);
-#endif
     }
   }
   float* out = part + (long)blockIdx.x * Ci * (16 * NCB);
@@ -764,7 +718,7 @@ __global__ __launch_bounds__(256) void convt_small_co_wgrad_kernel(const float* 
 }
 
 // wgrad, round 5 (Wo % 4 == 0: the 64 x 64 and 128 x 128 decoders): the same products with the operands STAGED through LDS.  The kernel
-// above requests every MFMA operand as a 4-byte global load one group (21 MFMAs, 0.3 us) ahead of its use: ablations (scripts/convt_abl.sh)
+// above requests every MFMA operand as a 4-byte global load one group (21 MFMAs, 0.3 us) ahead of its use: ablations (profiles/r05_convt_abl.txt)
 // give 724 us at 4 096 images, 337 without the MFMAs, 269 for the MFMAs alone -- the two never overlap.  Here a wave owns CHUNKS of 16
 // consecutive pixels of one image row: their x rows (16 x Ci floats, contiguous) and the 3 x 6 dy row segments their patches come from
 // (36 floats each) arrive as 16-byte global loads -- six per lane and chunk, requested a whole chunk (84 MFMAs, 1.1 us) ahead into registers,

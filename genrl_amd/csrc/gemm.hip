@@ -46,51 +46,14 @@
 #include <type_traits>
 #include <vector>
 
-#ifdef GENRL_DBG_TIMING
-// per-wave phase cycle counts of the most recent launch: [slot = (block*16 + wave) % 65536][6]
-__device__ unsigned long long genrl_dbg_cycles[65536 * 6];
-extern "C" void genrl_dbg_read(unsigned long long* out, int nslots) {
-  hipMemcpyFromSymbol(out, HIP_SYMBOL(genrl_dbg_cycles), sizeof(unsigned long long) * 6 * nslots);
-}
-#endif
-#ifndef RR_VEC_EPI
-#define RR_VEC_EPI 1   /* sgemm_rr_kernel: swapped MFMA operands -> 16-byte C stores (0 = scalar stores) */
-#endif
-#ifndef RR_PAIRLOOP
-#define RR_PAIRLOOP 1
-#endif
-#ifndef RR_SPREAD_READS
-#define RR_SPREAD_READS 1
-#endif
-#ifndef RR_LAST
-#define RR_LAST(WB) ((WB) == 2 ? RR_LAST2 : RR_LAST4)   /* MFMA steps left behind the second barrier of an iteration */
-#endif
-#ifndef RR_LAST2
-#define RR_LAST2 8
-#endif
-#ifndef RR_LAST4
-#define RR_LAST4 8
-#endif
-#ifndef RR_LDS_BUFS
-#define RR_LDS_BUFS 1   /* LDS tile images of sgemm_rr_kernel: 1 (two barriers per iteration) or 2 = ping-pong (one barrier; measured equal) */
-#endif
-#ifndef GENRL_RR_PD4
-#define GENRL_RR_PD4(WB) 2   /* register sets (tiles in flight) of sgemm_rr_kernel */
-#endif
-#ifndef GENRL_MID_TILES
-#define GENRL_MID_TILES 512    /* 64x64 tiles from which the 256-thread variant of the small tile is used */
-#endif
-#ifndef GENRL_SKINNY_MAX_M
-#define GENRL_SKINNY_MAX_M 32   /* rows up to which the weight-streaming kernel replaces the tiled GEMM */
-#endif
-#ifndef GENRL_BIG_WAVES
-#define GENRL_BIG_WAVES 3   /* min waves per SIMD requested for the 128x128 tile (register budget 512/n) */
-#endif
-#ifndef GENRL_MID_AT
-#define GENRL_MID_AT 3   /* staging after MFMA pair 3 of the 8 per step (KS/2 - 1 = last = old order) */
-#endif
-
 namespace {
+
+constexpr int RR_TAIL = 8;          // sgemm_rr_kernel: MFMA steps left behind the second barrier of an iteration
+constexpr int RR_PDEPTH = 2;        // sgemm_rr_kernel: register sets (tiles in flight)
+constexpr int MID_TILES = 512;      // 64x64 tiles from which the 256-thread variant of the small tile is used
+constexpr int SKINNY_MAX_M = 32;    // rows up to which the weight-streaming kernel replaces the tiled GEMM (GENRL_SKINNY_MAX_M overrides)
+constexpr int BIG_WAVES = 3;        // min waves per SIMD requested for the 128x128 tile (register budget 512/n)
+constexpr int MID_AT = 3;           // sgemm_kernel: staging after MFMA pair 3 of the 8 per step
 
 // Implicit stride-2 convolution operand (no materialised patch matrix): the logical row of pixel
 // m = (n, oy, ox) is the k x k x C patch of an NHWC image, i.e. k segments of seg_len = k*C
@@ -117,7 +80,7 @@ __device__ __forceinline__ int fdiv(int x, int d, float inv) {
 }
 
 template <int BM, int BN, int BK, int KG, int PD, bool FAST, bool A_KC, bool B_KC, int G = 0>
-__global__ __launch_bounds__(64 * (BM >= 64 ? 2 : 1) * (BN >= 64 ? 2 : 1) * KG, (BM == 128 && KG == 1) ? GENRL_BIG_WAVES : 1) void sgemm_kernel(
+__global__ __launch_bounds__(64 * (BM >= 64 ? 2 : 1) * (BN >= 64 ? 2 : 1) * KG, (BM == 128 && KG == 1) ? BIG_WAVES : 1) void sgemm_kernel(
     const float* __restrict__ A, long a_ld, const float* __restrict__ B, long b_ld,
     float* __restrict__ C, long ldc, const float* __restrict__ bias, int M, int N, int Ktot,
     int accumulate, int a_vec, int b_vec, int tiles_n, int ntiles, int k_per_split, float* __restrict__ ws,
@@ -301,15 +264,11 @@ __global__ __launch_bounds__(64 * (BM >= 64 ? 2 : 1) * (BN >= 64 ? 2 : 1) * KG, 
       store_tile(Bs + buf * B_SZ, LDB, B_KC, BN, v, tid + i * NT);
     }
   };
-  // MFMAs of one BK step from LDS buffer `buf`; `mid()` runs after the first half has been issued.
+  // MFMAs of one BK step from LDS buffer `buf`; `mid()` runs after MFMA pair MID_AT.
   // The register->LDS staging of the next tile goes there: queued MFMAs keep the matrix pipe busy while
   // the wave does its LDS stores and walks into the barrier, instead of the whole workgroup draining the
-  // pipe first (staging after the last MFMA left it idle for the store + barrier + first-read latency
-  // of every step).
-  // MFMAs of one BK step from LDS buffer `buf`; `mid()` runs after MFMA pair GENRL_MID_AT.
-  // The register->LDS staging of the next tile goes there: queued MFMAs keep the matrix pipe busy while
-  // the wave does its LDS stores and walks into the barrier, instead of the whole workgroup draining the
-  // pipe first.  Operands come in groups of 4 MFMA k-pairs (8 k per k-group slice): one ds_read_b128 per
+  // pipe first (staging after the last MFMA left it idle for the store + barrier + first-read latency of
+  // every step).  Operands come in groups of 4 MFMA k-pairs (8 k per k-group slice): one ds_read_b128 per
   // k-contiguous operand fragment, four 4-byte reads per row-contiguous one.
   auto compute = [&](int buf, auto&& mid) {
     constexpr int NG = KS / 8;
@@ -371,7 +330,7 @@ __global__ __launch_bounds__(64 * (BM >= 64 ? 2 : 1) * (BN >= 64 ? 2 : 1) * KG, 
 #pragma unroll
           for (int jn = 0; jn < TN; ++jn)
             acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[cur][i][e], gb[cur][jn][e], acc[i][jn], 0, 0, 0);
-        if (4 * j + e == GENRL_MID_AT) mid();
+        if (4 * j + e == MID_AT) mid();
       }
       if (!PRELOAD) __builtin_amdgcn_sched_barrier(0);
     }
@@ -380,49 +339,28 @@ __global__ __launch_bounds__(64 * (BM >= 64 ? 2 : 1) * (BN >= 64 ? 2 : 1) * KG, 
   // Software pipeline (register stages alternate, LDS double-buffered, one barrier per BK):
   //   step kt: issue global loads of tile kt+2 | MFMA on LDS[kt&1] | registers(tile kt+1) -> LDS[(kt+1)&1]
   // so a global load has a whole step plus an MFMA phase to land before it is consumed.
-#ifdef GENRL_DBG_TIMING
-  long long tacc[6] = {0, 0, 0, 0, 0, 0};
-  long long tlast = __builtin_readcyclecounter();
-#define TICK(i)                                        \
-  {                                                    \
-    const long long now__ = __builtin_readcyclecounter(); \
-    tacc[i] += now__ - tlast;                          \
-    tlast = now__;                                     \
-  }
-#else
-#define TICK(i)
-#endif
   if (PD == 2) {
     fetch(0, 0);                  // both leading tiles are requested back-to-back: one exposed
     if (nk > 1) fetch(1, 1);      // memory latency in the prologue instead of two
     stage(0, 0);
     __syncthreads();
-    TICK(4);
     for (int kt = 0; kt < nk; kt += 2) {
       // LDS[0] holds tile kt, register stage 1 holds tile kt+1.  The next global loads are issued
       // AFTER this step's MFMAs are queued: right after the barrier every wave of the workgroup
       // would hit the CU's single address unit at once (32 KB per step = 512 issue cycles) with the
       // MFMA pipe idle; behind the MFMAs the waves arrive staggered and the issue is hidden.
-      TICK(0);
       compute(0, [&]() {
         if (kt + 2 < nk) fetch(0, kt + 2);
         if (kt + 1 < nk) stage(1, 1);
       });
-      TICK(1);
-      TICK(2);
       __syncthreads();
-      TICK(3);
       if (kt + 1 >= nk) break;
       // LDS[1] holds tile kt+1, register stage 0 holds tile kt+2
-      TICK(0);
       compute(1, [&]() {
         if (kt + 3 < nk) fetch(1, kt + 3);
         if (kt + 2 < nk) stage(0, 0);
       });
-      TICK(1);
-      TICK(2);
       __syncthreads();
-      TICK(3);
     }
   } else {   // one tile ahead (fewer registers: keeps the 128x128 shape at 3 waves/SIMD)
     fetch(0, 0);
@@ -435,10 +373,6 @@ __global__ __launch_bounds__(64 * (BM >= 64 ? 2 : 1) * (BN >= 64 ? 2 : 1) * KG, 
     }
   }
 
-#ifdef GENRL_DBG_NO_EPILOGUE
-  if (acc[0][0][0] == 12345.678f) C[0] = acc[0][0][1];
-  return;
-#endif
   // ---- sum the KG partial tiles through LDS (the operand buffers are dead after the last barrier)
   // and store.  Every k-group takes part: group g owns accumulator registers [g*16/KG, (g+1)*16/KG)
   // of each 32x32 tile (= a set of output rows), receives the other groups' partials for them
@@ -488,11 +422,7 @@ __global__ __launch_bounds__(64 * (BM >= 64 ? 2 : 1) * (BN >= 64 ? 2 : 1) * KG, 
       for (int r = 0; r < 16; ++r) {
         if (KG > 1 && (r / RPG) != kg) continue;
         const int row = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-#ifdef GENRL_DBG_NO_STORE
-        if (row < M && acc[i][j][r] == 12345.678f) {
-#else
         if (row < M) {
-#endif
           float* c = C + (long)row * ldc + col;
           float v = acc[i][j][r] + bv;
           if (accumulate) v += *c;
@@ -500,13 +430,6 @@ __global__ __launch_bounds__(64 * (BM >= 64 ? 2 : 1) * (BN >= 64 ? 2 : 1) * KG, 
         }
       }
     }
-#ifdef GENRL_DBG_TIMING
-  TICK(5);
-  if (lane == 0) {
-    const int slot = ((blockIdx.y * gridDim.x + blockIdx.x) * (int)(blockDim.x >> 6) + wave) & 65535;
-    for (int i = 0; i < 6; ++i) genrl_dbg_cycles[slot * 6 + i] = (unsigned long long)tacc[i];
-  }
-#endif
 }
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -574,13 +497,13 @@ __global__ __launch_bounds__(256, 2) void sgemm_rr_kernel(
   constexpr int BM = 32 * WBM, BN = 32 * WBN, BK = WB == 2 ? 64 : 32, NT = 256;
   constexpr int NVA = BM * BK / 4 / NT, NVB = BN * BK / 4 / NT;     // float4 per thread per operand (3 or 4)
   constexpr int NJ = BK / 16, KV = BK / 4, RVA = BM / 4, RVB = BN / 4;   // k-groups of 16; vectors per k-row / per tile row
-  constexpr int PDEPTH = GENRL_RR_PD4(WB);
+  constexpr int PDEPTH = RR_PDEPTH;
   constexpr int WTM = 16 * WBM, WTN = 16 * WBN;                     // wave tile
   static_assert(BM * BK / 4 % NT == 0 && BN * BK / 4 % NT == 0, "tile operands must split evenly over the threads");
   constexpr int LDA = A_KC ? BK + 4 : BM + 4, LDB = B_KC ? BK + 4 : BN + 4;
   constexpr int A_SZ = A_KC ? BM * LDA : BK * LDA, B_SZ = B_KC ? BN * LDB : BK * LDB;
   constexpr int T_SZ = A_SZ + B_SZ;                                 // one tile image; two of them (ping-pong)
-  __shared__ __attribute__((aligned(16))) float lds[RR_LDS_BUFS * T_SZ];
+  __shared__ __attribute__((aligned(16))) float lds[T_SZ];
   int bid = blockIdx.x, tile_m, tile_n;
   {
     const int x = bid % 8, i = bid / 8;
@@ -821,34 +744,23 @@ __global__ __launch_bounds__(256, 2) void sgemm_rr_kernel(
       for (int t = (BF == 3 ? 0 : 5); t < 6; ++t)
 #pragma unroll
         for (int bj = 0; bj < WBN; ++bj)
-#if RR_VEC_EPI
           acc[bi][bj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, b3c[bj][TY[t]]),
                                                                 __builtin_bit_cast(bf16x8_t, a3[TX[t]]), acc[bi][bj], 0, 0, 0);
-#else
-          acc[bi][bj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a3[TX[t]]),
-                                                                __builtin_bit_cast(bf16x8_t, b3c[bj][TY[t]]), acc[bi][bj], 0, 0, 0);
-#endif
       return;
     }
 #pragma unroll
     for (int bj = 0; bj < WBN; ++bj)
-#if RR_VEC_EPI
       acc[bi][bj] = __builtin_amdgcn_mfma_f32_16x16x4f32(fb[j][bj][e], fa[j][bi][e], acc[bi][bj], 0, 0, 0);
-#else
-      acc[bi][bj] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[j][bi][e], fb[j][bj][e], acc[bi][bj], 0, 0, 0);
-#endif
   };
   constexpr int NSTEP = NJ * 4 * WBM, PRE = 4 * WBM, UEVERY = WB == 2 ? 2 : 1, NVT = NVA + NVB;
-  constexpr int LAST = RR_LAST(WB) < NSTEP - PRE - NVT * UEVERY ? RR_LAST(WB) : NSTEP - PRE - NVT * UEVERY;
+  constexpr int LAST = RR_TAIL < NSTEP - PRE - NVT * UEVERY ? RR_TAIL : NSTEP - PRE - NVT * UEVERY;
   static_assert(LAST >= 1 && (NSTEP - PRE - LAST) >= NVT * UEVERY, "not enough MFMA steps to interleave the staging");
   read_frags(lds, 0);
-  auto iteration = [&](int kt, auto ST, auto CUR) {
+  auto iteration = [&](int kt, auto ST) {
     constexpr int st = decltype(ST)::value;     // register set holding tile kt+1; refilled with tile kt+1+PDEPTH
-    constexpr int cur = RR_LDS_BUFS == 2 ? decltype(CUR)::value : 0, nxt = RR_LDS_BUFS == 2 ? 1 - cur : 0;
-    const float* Tc = lds + cur * T_SZ;         // image of tile kt
-    float* Tn = lds + nxt * T_SZ;               // image of tile kt+1 (the same buffer when single-buffered)
+    const float* Tc = lds;                      // image of tile kt
+    float* Tn = lds;                            // image of tile kt+1 (the same buffer, refilled after barrier 2)
     // 1. the rest of tile kt's fragments -> registers, behind the MFMAs of k-group 0
-#if RR_SPREAD_READS
     // (requested one (j, bi) pair at a time between the MFMA steps, so that the LDS never sees the four waves'
     // whole fragment sets at once and the wait in front of the barrier below is already satisfied)
     constexpr int WBX = WBM > WBN ? WBM : WBN, NU = (NJ - 1) * WBX;
@@ -863,13 +775,7 @@ __global__ __launch_bounds__(256, 2) void sgemm_rr_kernel(
       step(sidx);
       __builtin_amdgcn_sched_barrier(0);
     }
-#else
-#pragma unroll
-    for (int j = 1; j < NJ; ++j) read_frags(Tc, j);
-#pragma unroll
-    for (int sidx = 0; sidx < PRE; ++sidx) step(sidx);
-#endif
-    if (RR_LDS_BUFS == 1) __syncthreads(); // 2. (single buffer) the LDS tile is dead: refill it behind the following MFMAs
+    __syncthreads();                       // 2. the LDS tile is dead: refill it behind the following MFMAs
     // one staged vector goes to LDS after each of the first NVA+NVB (every UEVERY-th) steps and its registers are
     // re-armed with the load for a later tile.  Everything is unconditional (clamped addresses are always
     // valid; the final iterations stage data nobody reads): one basic block, counted waits.
@@ -913,23 +819,15 @@ __global__ __launch_bounds__(256, 2) void sgemm_rr_kernel(
     }
   };
   using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  // (register set and LDS buffer parities are compile-time: iterations come in pairs, one basic block per pair —
-  // a conditional second half makes the register allocator rotate the staged sets through copies, and a copy
-  // waits for its load a whole iteration early)
-#if RR_PAIRLOOP
+  // (register set parities are compile-time: iterations come in pairs, one basic block per pair — a conditional
+  // second half makes the register allocator rotate the staged sets through copies, and a copy waits for its
+  // load a whole iteration early)
   int kt = 0;
   for (; kt + 1 < nk; kt += 2) {
-    iteration(kt, std::integral_constant<int, PDEPTH - 1>{}, I0{});
-    iteration(kt + 1, I0{}, I1{});
+    iteration(kt, std::integral_constant<int, PDEPTH - 1>{});
+    iteration(kt + 1, I0{});
   }
-  if (kt < nk) iteration(kt, std::integral_constant<int, PDEPTH - 1>{}, I0{});
-#else
-  for (int kt = 0; kt < nk; kt += 2) {
-    iteration(kt, std::integral_constant<int, PDEPTH - 1>{}, I0{});
-    if (kt + 1 < nk) iteration(kt + 1, I0{}, I1{});
-  }
-#endif
+  if (kt < nk) iteration(kt, std::integral_constant<int, PDEPTH - 1>{});
 
   if constexpr (BF == 3) {
     // 32x32 blocks, operands swapped: lane (l32, h32), register v = C[row = l32][col = 8 (v/4) + 4 h32 + v%4]
@@ -975,7 +873,6 @@ __global__ __launch_bounds__(256, 2) void sgemm_rr_kernel(
     }
     return;
   }
-#if RR_VEC_EPI
   // ---- epilogue.  The MFMAs are issued with the operands swapped (B fragment first), so a 16x16 block holds
   // its TRANSPOSE in the D layout: lane (l16, q4), register v = C[row = l16][col = 4*q4 + v] -> every lane owns
   // 4 consecutive columns of one row and stores them with one 16-byte instruction.
@@ -1011,25 +908,6 @@ __global__ __launch_bounds__(256, 2) void sgemm_rr_kernel(
       }
     }
   }
-#else
-#pragma unroll
-  for (int bi = 0; bi < WBM; ++bi)
-#pragma unroll
-    for (int bj = 0; bj < WBN; ++bj) {
-      const int col = n0 + wn0 + 16 * bj + l16;
-      if (col >= N) continue;
-      const float bv = bias ? bias[col] : 0.f;
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const int row = m0 + wm0 + 16 * bi + 4 * q4 + v;
-        if (row >= M) continue;
-        float* c = C + (long)row * ldc + col;
-        float val = acc[bi][bj][v] + bv;
-        if (accumulate) val += *c;
-        *c = val;
-      }
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1275,21 +1153,9 @@ __global__ __launch_bounds__(1024) void skinny_kernel(const float* __restrict__ 
   }
 }
 
-#ifndef GENRL_SMALL_PD
-#define GENRL_SMALL_PD 2
-#endif
-#ifndef GENRL_SMALL_BK
-#define GENRL_SMALL_BK 64
-#define GENRL_SMALL_KG 4
-#endif
-#ifndef GENRL_BIG_PD
-#define GENRL_BIG_PD 1
-#endif
-#ifndef GENRL_BIG_BK
-#define GENRL_BIG_BK 16
-#define GENRL_BIG_KG 1
-#endif
-constexpr int SMALL_BK = GENRL_SMALL_BK, SMALL_KG = GENRL_SMALL_KG;
+// sgemm_kernel tile configurations: BK, k-groups and register stages of the 64x64 and 128x128 tiles
+constexpr int SMALL_BK = 64, SMALL_KG = 4, SMALL_PD = 2;
+constexpr int BIG_BK = 16, BIG_KG = 1, BIG_PD = 1;
 
 // Launch plan: tile configuration + split-K count, from a small cost model.  All workgroups of a
 // launch do equal work, so they run in ceil(WGs / slots) rounds: a WG count just above a multiple of
@@ -1314,7 +1180,7 @@ inline bool force_mid() {       // calibration only: GENRL_GEMM_FORCE=m,<splits>
   static const char* f = getenv("GENRL_GEMM_FORCE");
   return f && f[0] == 'm';
 }
-constexpr int BIG_WG_PER_CU = GENRL_BIG_KG == 1 ? GENRL_BIG_WAVES : 2;   // 256-thread WGs: one wave per SIMD each
+constexpr int BIG_WG_PER_CU = BIG_KG == 1 ? BIG_WAVES : 2;   // 256-thread WGs: one wave per SIMD each
 inline double reduce_cost(long sp, long M, long N) { return sp > 1 ? 5.0 + (double)sp * M * N * 4.0 / 3.0e6 : 0.0; }
 inline SplitPlan plan_split(int M, int N, int K) {
   static const char* force = getenv("GENRL_GEMM_FORCE");   // calibration only: "s,<splits>" / "b,<splits>"
@@ -1324,7 +1190,7 @@ inline SplitPlan plan_split(int M, int N, int K) {
   if (force) {
     p.big = force[0] == 'b';
     const long s = force[0] && force[1] == ',' ? atol(force + 2) : 1;   // ("m" alone: no count to read past its end)
-    const int bk = p.big ? GENRL_BIG_BK : SMALL_BK;
+    const int bk = p.big ? BIG_BK : SMALL_BK;
     p.k_per_split = cdiv(cdiv(K, s > 0 ? s : 1), bk) * bk;
     p.splits = cdiv(K, p.k_per_split);
     return p;
@@ -1347,7 +1213,6 @@ inline SplitPlan plan_split(int M, int N, int K) {
     }
     if (smax < 1) best = cdiv(tiles, 256) * (t_fixed + K * t_k), p = SplitPlan{0, 1, K};
   }
-#ifndef GENRL_NO_BIG_SPLIT
   // ---- big configuration with split-K (few output tiles, long K)
   if (K >= 2048) {
     const double t_fixed = 6.0, t_k = 0.060;   // (sustained long-K rate is a little better than the 64x64 tile)
@@ -1365,7 +1230,6 @@ inline SplitPlan plan_split(int M, int N, int K) {
       }
     }
   }
-#endif
   if (p.splits <= 1) p.splits = 1, p.k_per_split = K;
   return p;
 }
@@ -1586,8 +1450,7 @@ static int sgemm_impl(const float* A, long a_rs, long a_ks, const float* B, long
   if (M <= 0 || N <= 0) return GENRL_OK;
   if (K <= 0 || (a_rs != 1 && a_ks != 1) || (b_rs != 1 && b_ks != 1)) return GENRL_EINVAL;
   hipStream_t s = static_cast<hipStream_t>(stream);
-#ifndef GENRL_NO_SKINNY
-  static const int skinny_max_m = getenv("GENRL_SKINNY_MAX_M") ? atoi(getenv("GENRL_SKINNY_MAX_M")) : GENRL_SKINNY_MAX_M;
+  static const int skinny_max_m = getenv("GENRL_SKINNY_MAX_M") ? atoi(getenv("GENRL_SKINNY_MAX_M")) : SKINNY_MAX_M;
   // M <= 32: always.  33 .. 128 rows with N, K <= 1024 (the rollout's 1024 -> 1024 layers at 4 sequences per GPU): row groups
   // of 32 give 256 workgroups and one launch where the 64x64 tiles need a K split + reduce launch (7.8 vs 11.0 us measured;
   // longer K or wider N favour the tiles again: scripts/small_m.py)
@@ -1619,7 +1482,6 @@ static int sgemm_impl(const float* A, long a_rs, long a_ks, const float* B, long
     GENRL_CHECK_LAUNCH();
     return GENRL_OK;
   }
-#endif
   // tall stream with a register-resident B (see sgemm_tall_kernel)
   if (!p16 && G == 0 && a_ks == 1 && M >= 16384 && K <= 112 && K >= 4 && (K & 3) == 0 && (a_rs & 3) == 0 && (ldc & 3) == 0 &&
       ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(C)) & 15) == 0 && use_tall()) {
@@ -1667,7 +1529,7 @@ static int sgemm_impl(const float* A, long a_rs, long a_ks, const float* B, long
                          wsp, s, G, gp)) >= 0)
     ;
   else if (p.big && (trace_fallback(M, N, K, a_rs, a_ks, b_rs, b_ks, A, B), true))
-    rc = launch_cfg<128, 128, GENRL_BIG_BK, GENRL_BIG_KG, GENRL_BIG_PD>(A, a_rs, a_ks, B, b_rs, b_ks, C, ldc, bias, M, N, K, accumulate,
+    rc = launch_cfg<128, 128, BIG_BK, BIG_KG, BIG_PD>(A, a_rs, a_ks, B, b_rs, b_ks, C, ldc, bias, M, N, K, accumulate,
                                                             p.splits, p.k_per_split, wsp, s, G, gp);
   else if (use_rr(M, N, K, p.splits) && (rc = launch_rr<2>(A, a_rs, a_ks, B, b_rs, b_ks, C, ldc, bias, M, N, K, accumulate, p.splits,
                                        (p.k_per_split + 63) / 64 * 64, wsp, s, G, gp)) >= 0)
@@ -1675,13 +1537,13 @@ static int sgemm_impl(const float* A, long a_rs, long a_ks, const float* B, long
   else if (trace_fallback(M, N, K, a_rs, a_ks, b_rs, b_ks, A, B), false)
     ;
 
-  else if ((p.splits == 1 && (long)cdiv(M, 64) * cdiv(N, 64) >= GENRL_MID_TILES) || force_mid())
+  else if ((p.splits == 1 && (long)cdiv(M, 64) * cdiv(N, 64) >= MID_TILES) || force_mid())
     // several 64x64 tiles per CU: 256-thread workgroups (one wave per SIMD each, 4+ resident per CU,
     // independent barriers) beat the single 1024-thread workgroup per CU by 10-13 % (measured)
     rc = launch_cfg<64, 64, 16, 1, 2>(A, a_rs, a_ks, B, b_rs, b_ks, C, ldc, bias, M, N, K, accumulate, p.splits,
                                       p.k_per_split, wsp, s, G, gp);
   else
-    rc = launch_cfg<64, 64, SMALL_BK, SMALL_KG, GENRL_SMALL_PD>(A, a_rs, a_ks, B, b_rs, b_ks, C, ldc, bias, M, N, K,
+    rc = launch_cfg<64, 64, SMALL_BK, SMALL_KG, SMALL_PD>(A, a_rs, a_ks, B, b_rs, b_ks, C, ldc, bias, M, N, K,
                                                                accumulate, p.splits, p.k_per_split, wsp, s, G, gp);
   if (rc || !split) return rc;
   const long MN = (long)M * N;

@@ -44,10 +44,6 @@ typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef PLANES_ABL
-#define PLANES_ABL 0
-#endif
-
 namespace {
 
 struct PlaneSeg {
@@ -116,15 +112,9 @@ __device__ __forceinline__ float pow2_ratio(float a, float b) {
 // the inverse scale h2_inv_of gives an all-zero row, and only such a row (2^-123)
 __device__ __forceinline__ bool zero_row_inv(float inv) { return __builtin_bit_cast(unsigned, inv) == (4u << 23); }
 
-#ifndef LNE_ABL
-#define LNE_ABL 0      /* ablations of the LayerNorm epilogue (scripts/gemm_ln_abl.sh): 1 no y / plane stores, 2 no wait for the peers' records, 3 no SiLU, 4 no pre-activation store */
-#endif
-#ifndef PLANES_DMA_AUX
-#define PLANES_DMA_AUX 0      /* cache policy bits of the operand DMAs (experiments: 2 = nt) */
-#endif
 __device__ __forceinline__ void glds16(const void* g, unsigned lds_byte_addr) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)(uintptr_t)lds_byte_addr, 16, 0, PLANES_DMA_AUX);
+                                   (__attribute__((address_space(3))) void*)(uintptr_t)lds_byte_addr, 16, 0, 0);
 }
 
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory"); }
@@ -150,11 +140,11 @@ __global__ __launch_bounds__(256, (TM * TN == 1 && NS == 2 && FMT == 1) ? 2 : 1)
   constexpr int NPA = APIECES / 2, NPB = BPIECES / 2;  // pieces per wave (waves 0,1: A; waves 2,3: B)
   constexpr int NPMAX = NPA > NPB ? NPA : NPB;
   constexpr int KS = BK / 16;                          // MFMA k-steps per stage
-  // PF > 0 (experiment, -DPLANES_EXPERIMENTS): every stage's DMAs are preceded by an L2 PREFETCH of the stage PF further on -- one
+  // PF > 0 (experiment; no launch uses it): every stage's DMAs are preceded by an L2 PREFETCH of the stage PF further on -- one
   // 4-byte LDS-DMA per 128-byte line (NPF wave-instructions per wave) into a 1 KiB dummy area -- to test whether the K loop waits on
   // L2 misses (operands are never L2-resident at a kernel's start).  It does not: 1024^3 takes 14.1-15.7 us with the prefetch against
-  // 12.2-13.4 without, on warm and on cold operands alike, and rings of 4 / 5 stages change nothing either (scripts/cold_bench.py,
-  // profiles/r03_inshape.txt).  The loop runs at the L2 -> LDS delivery rate of this access pattern (~17 TB/s over the chip).
+  // 12.2-13.4 without, on warm and on cold operands alike, and rings of 4 / 5 stages change nothing either
+  // (profiles/r03_inshape.txt).  The loop runs at the L2 -> LDS delivery rate of this access pattern (~17 TB/s over the chip).
   static_assert(PF == 0 || (BK == 64 && !CONV), "prefetch: 128-byte tile rows, plain operands");
   constexpr int NPF = PF ? TM : 0;
   // h2: the epilogue's factors -- inverse row scales of both operands, bias -- are fetched by three LDS-DMAs per 64 rows / columns
@@ -164,9 +154,6 @@ __global__ __launch_bounds__(256, (TM * TN == 1 && NS == 2 && FMT == 1) ? 2 : 1)
   // LNE: gamma / beta of all N <= 1024 columns (2 x 4 KiB), reduction scratch
   constexpr int LN_AT = EPI_AT + EPI, LN_G = LN_AT, LN_B = LN_AT + 4096, LN_R = LN_AT + 8192, LN_U = LN_AT + 9216, LN_T = LN_AT + 9472, LN_BYTES = LNE ? 9728 : 0;
   __shared__ __attribute__((aligned(1024))) unsigned char lds[EPI_AT + EPI + LN_BYTES];
-#if PLANES_ABL == 6       /* ablation 6 (scripts/intercept64.py): the launch alone -- same grid, LDS and register footprint, no work */
-  if (M > 0) { if (threadIdx.x == 1023) lds[0] = 0; return; }
-#endif
 
   // XCD-aware tile order (workgroup b runs on XCD b % 8; each XCD gets a compact sub-block of the tile grid)
   int bid = blockIdx.x, tile_m, tile_n;
@@ -308,16 +295,12 @@ __global__ __launch_bounds__(256, (TM * TN == 1 && NS == 2 && FMT == 1) ? 2 : 1)
     const int s = m / (NPROD * TM * TN), t = (m / (TM * TN)) % NPROD, i = (m / TN) % TM, j = m % TN;
     f32x16& c = acc[(FMT || NACC == 3) ? CL[t] : 0][i][j];
     // operands swapped (B first): the block holds its transpose in the D layout -> 16-byte C stores
-#if PLANES_ABL == 1       /* ablation: no MFMAs (fragments kept live) */
-    asm volatile("" ::"v"(fr[set][s][TM + j][PB[t]]), "v"(fr[set][s][i][PA[t]]));
-#else
     if constexpr (FMT == 0)
       c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fr[set][s][TM + j][PB[t]]),
                                                   __builtin_bit_cast(bf16x8_t, fr[set][s][i][PA[t]]), c, 0, 0, 0);
     else
       c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, fr[set][s][TM + j][PB[t]]),
                                                  __builtin_bit_cast(f16x8_t, fr[set][s][i][PA[t]]), c, 0, 0, 0);
-#endif
   };
 
   const float* const ainv_l = s1.k ? s1.a_inv : s0.a_inv;       // (the epilogue undoes the scaling of the LAST segment)
@@ -477,11 +460,9 @@ __global__ __launch_bounds__(256, (TM * TN == 1 && NS == 2 && FMT == 1) ? 2 : 1)
     for (int m = 0; m < KB; ++m) mfma_one(set, m);
     __builtin_amdgcn_sched_barrier(0);
     // stage t+1 landed (own DMAs; stages t+2 .. stay in flight); all fragment reads of stage t have returned
-#if PLANES_ABL != 5      /* ablation 5: no barrier either */
     wait_vm<(NS - 2) * (NP + NPF)>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-#endif
     __builtin_amdgcn_sched_barrier(0);
     prefetch();
 #pragma unroll
@@ -493,13 +474,9 @@ __global__ __launch_bounds__(256, (TM * TN == 1 && NS == 2 && FMT == 1) ? 2 : 1)
         if (o >= NSIDE) continue;
         // ops 0 .. 3 NP-1: read, read, DMA, read, read, DMA, ...; the rest: reads
         if (o < 3 * NP && o % 3 == 2) {
-#if PLANES_ABL != 2 && PLANES_ABL < 4     /* ablation 2: no DMA in the loop; 4, 5: neither DMA nor reads */
           issue_one(buf3, o / 3);
-#endif
         } else {
-#if PLANES_ABL != 3 && PLANES_ABL < 4     /* ablation 3: no fragment reads in the loop */
           read_one(1 - set, o < 3 * NP ? o - o / 3 : o - NP, buf1);
-#endif
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -517,22 +494,11 @@ __global__ __launch_bounds__(256, (TM * TN == 1 && NS == 2 && FMT == 1) ? 2 : 1)
       self(self, std::integral_constant<int, p + 1>{}, guarded);
     }
   };
-#if PLANES_ABL < 7         /* ablations 7 .. 10: no K loop at all (7: no epilogue either; 9: epilogue without its stores; 10: non-temporal stores) */
   while (it + PERIOD <= nk) run(run, std::integral_constant<int, 0>{}, false);
   run(run, std::integral_constant<int, 0>{}, true);
-#else
-  asm volatile("" ::"v"(fr[0][0][0][0]), "v"(fr[0][KS - 1][NB_ - 1][NPL - 1]));
-#endif
   // (the ring's last slots were issued as re-reads of the final stage into buffers nobody reads: they are drained at the very END of
   // the kernel -- no DMA may be in flight into this workgroup's LDS when it exits -- so that their round trip runs under the epilogue;
-  // the epilogue's own LDS words sit outside the ring and were covered by the first barrier.  scripts/intercept64.py: -0.x us per launch)
-#if PLANES_ABL == 7
-  wait_vm<0>();
-  if (M > 0) return;
-#endif
-#ifdef PLANES_EARLY_DRAIN
-  wait_vm<0>();
-#endif
+  // the epilogue's own LDS words sit outside the ring and were covered by the first barrier.  -0.1 to -0.2 us per launch)
 
   if constexpr (LNE) {
     // ---- LayerNorm (+ SiLU) epilogue (see LnEpi).  Lane (l32, h32) of wave (wm, wn) holds row wm 32 + l32, columns wn 32 + 8 gq + 4 h32 + v.
@@ -586,7 +552,7 @@ __global__ __launch_bounds__(256, (TM * TN == 1 && NS == 2 && FMT == 1) ? 2 : 1)
       *reinterpret_cast<f32x4*>(part_rb + (tile_n * 64 + rl) * 4) = f32x4{mean_t, tagf, m2, tagf};
     }
     // (while the peers arrive) the pre-activation for the backward, and the scale bound from gamma / beta of all N columns
-    if (row < M && LNE_ABL != 4) {
+    if (row < M) {
 #pragma unroll
       for (int gq = 0; gq < 4; ++gq) {
         const int col = n0 + wn * 32 + 8 * gq + 4 * h32;
@@ -628,7 +594,7 @@ __global__ __launch_bounds__(256, (TM * TN == 1 && NS == 2 && FMT == 1) ? 2 : 1)
           const float t1 = rec[jt][1], t3 = rec[jt][3];
           all = all && (__builtin_bit_cast(unsigned, t1) == tag) && (__builtin_bit_cast(unsigned, t3) == tag);
         }
-        if (__all(all) || LNE_ABL == 2) { ok = true; break; }
+        if (__all(all)) { ok = true; break; }
         __builtin_amdgcn_s_sleep(2);
       }
       if (!ok) {          // never silently wrong: the failure word for the host, NaN rows for whoever reads the results first
@@ -667,15 +633,10 @@ __global__ __launch_bounds__(256, (TM * TN == 1 && NS == 2 && FMT == 1) ? 2 : 1)
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
           const float z = (o[4 * gq + v] - mu) * rs * g[v] + b[v];
-          y[v] = (ln.act && LNE_ABL != 3) ? siluf_(z) : z;
+          y[v] = ln.act ? siluf_(z) : z;
         }
-#if LNE_ABL == 1
-        asm volatile("" ::"v"(y[0]), "v"(y[1]), "v"(y[2]), "v"(y[3]));
-        if (ln.yp && u_sc == 123.f) {
-#else
         if (ln.y) *reinterpret_cast<float4*>(ln.y + (long)row * ln.ldy + col) = make_float4(y[0], y[1], y[2], y[3]);
         if (ln.yp) {
-#endif
           h2_u32x2 hh, ll;
           unsigned a, bq;
           h2_split2(y[0] * u_sc, y[1] * u_sc, a, bq); hh[0] = a; ll[0] = bq;
@@ -744,14 +705,7 @@ __global__ __launch_bounds__(256, (TM * TN == 1 && NS == 2 && FMT == 1) ? 2 : 1)
             const float4 cv = *reinterpret_cast<const float4*>(c);
             o[0] += cv.x; o[1] += cv.y; o[2] += cv.z; o[3] += cv.w;
           }
-#if PLANES_ABL == 9
-          asm volatile("" ::"v"(o[0]), "v"(o[1]), "v"(o[2]), "v"(o[3]), "v"(c));
-#elif PLANES_ABL == 10 || defined(PLANES_NT_STORE)
-          __builtin_nontemporal_store(o[0], c); __builtin_nontemporal_store(o[1], c + 1);
-          __builtin_nontemporal_store(o[2], c + 2); __builtin_nontemporal_store(o[3], c + 3);
-#else
           *reinterpret_cast<float4*>(c) = make_float4(o[0], o[1], o[2], o[3]);
-#endif
           if constexpr (TM * TN == 1 && FMT == 1) {
 #pragma unroll
             for (int v = 0; v < 4; ++v) lg[4 * gq + v] = o[v];
@@ -830,12 +784,7 @@ __global__ __launch_bounds__(256, (TM * TN == 1 && NS == 2 && FMT == 1) ? 2 : 1)
 // MFMAs; u = 2b + 1 (l planes): the 32 h*l and l*h MFMAs.  Fragments: two h sets (alternating per block) and one l set, 64 registers
 // each (the kernel above holds two whole stages = 256); the reads of half stage u + 1 and the DMAs of half stage u + 4 go out
 // between the MFMAs of half-iteration u, one barrier per half-iteration.  One segment, FOLD-free, epilogue as above.
-#ifndef HL_KBH
-#define HL_KBH 2
-#endif
-#ifndef HL_KBL
-#define HL_KBL 2
-#endif
+constexpr int HL_KBH = 2, HL_KBL = 2;     // MFMAs of an h*h / an h*l half-iteration issued ahead of its barrier
 template <bool CONV>
 __global__ __launch_bounds__(256, 1) void gemm_planes_hl_kernel(PlaneSeg s0, float* __restrict__ C, long ldc, const float* __restrict__ bias,
                                                                 int M, int N, int accumulate, int tiles_m, int tiles_n, int xcd_m,
@@ -848,7 +797,7 @@ __global__ __launch_bounds__(256, 1) void gemm_planes_hl_kernel(PlaneSeg s0, flo
     int bid = blockIdx.x;
     const int ntiles = tiles_m * tiles_n;
     const int x = bid % 8, i = bid / 8;
-    const int order = xcd_m >> 8;          // experiments (GENRL_HL_ORDER): how an XCD walks its sub-block
+    const int order = xcd_m >> 8;          // how an XCD walks its sub-block: 0 row-major, 1 rounds in snake order, 2 column-major
     xcd_m &= 255;
     if (xcd_m > 0) {
       const int sub_m = tiles_m / xcd_m, sub_n = tiles_n / (8 / xcd_m);
@@ -1064,9 +1013,6 @@ __global__ __launch_bounds__(256, 1) void gemm_planes_hl_kernel(PlaneSeg s0, flo
     half_iter(std::integral_constant<int, 0>{});
     half_iter(std::integral_constant<int, 1>{});
   }
-#ifdef PLANES_EARLY_DRAIN
-  wait_vm<0>();
-#endif
 
   // ---- epilogue (as above, TM = TN = 2, NACC = 2); the ring's trailing re-read DMAs are drained behind it, at the kernel's end
   auto epi_f = [&](int idx) __attribute__((always_inline)) -> float {
@@ -1640,12 +1586,6 @@ __global__ __launch_bounds__(256) void split_h2_t_batch_kernel(SplitBatch b) {
 // GENRL_GEMM_LOG=<file> (common.h): h2 planes hold 4 bytes per operand element (two fp16 planes)
 static inline void log_launch(const char* family, long M, long N, long K, double bytes) { genrl_log_launch(family, M, N, K, bytes); }
 static inline double kk_bytes(long M, long N, long K) { return 4.0 * ((double)M * K + (double)N * K + (double)M * N); }
-// the 128x128 products on the plane-alternating kernel (gemm_planes_hl_kernel); GENRL_PLANES_HL=0: the two-whole-stages kernel
-// how an XCD walks its sub-block of 128 x 128 tiles (gemm_planes_hl_kernel).  1 (default since round 5): rounds of 8 row panels x 4 column
-// panels in snake order -- 16384 x 1024 x 1024 122.2 -> 116.8 us, 16384 x 1536 x 1024 180.2 -> 164.8, K = 2048 202.3 -> 197.0 against 0 =
-// row-major over the sub-block (rounds of 4 x 8); the L2-miss bytes do NOT change (201.8 MB per launch either way = the compulsory 6 MB per
-// round of 32 resident tiles: no operand survives from one round to the next in a 4 MiB L2), profiles/r05_hl_order.txt
-static int hl_order() { return 1; }
 // 128 x 192 tiles (gemm_planes_hlw_kernel) where they pad fewer columns than 128-wide ones (N = 192: the sub-pixel products' 4 x 48
 // columns); GENRL_HL_WIDE=0: never, 2: also where both tilings pad the same (N = 384, 768, 1536: fewer, larger tiles -- experiments)
 static bool use_wide(int N) {
@@ -1660,9 +1600,8 @@ static bool use_wide(int N) {
 static bool use_tall96(int N, int K) {
   return N <= 96 && K >= 1024;
 }
+// the 128x128 products on the plane-alternating kernel (gemm_planes_hl_kernel); GENRL_PLANES_HL=0: the two-whole-stages kernel
 static bool hl_on() { static const bool on = !getenv("GENRL_PLANES_HL") || getenv("GENRL_PLANES_HL")[0] != '0'; return on; }
-int g_planes_nosplit = 0;        // experiments: 1 = no row split against wave quantisation (GENRL_PLANES_NOSPLIT)
-int g_planes_variant = 0;        // experiments (scripts/cold_bench.py): ring depth / prefetch distance variants
 int g_planes_force_tile = 0;     // 0 auto, 1: 64x64, 2: 128x128 (experiments)
 
 }  // namespace
@@ -1681,7 +1620,6 @@ void genrl_log_launch(const char* family, long M, long N, long K, double operand
 }
 
 int genrl_planes_force_tile(int t) { const int p = g_planes_force_tile; g_planes_force_tile = t; return p; }
-int genrl_planes_variant(int v) { const int p = g_planes_variant; g_planes_variant = v; return p; }
 long genrl_planes_last_route(void) { return (long)g_planes_route | ((long)g_planes_route_splits << 32); }
 
 /* x (R x Cn fp32, row stride ldx) -> three bf16 planes [R][ld_out] (or [Cn][ld_out] when transpose), zero padded */
@@ -1804,7 +1742,7 @@ static int gemm_h2_impl(const uint16_t* a0, long a0_ld, long a0_plane, const flo
   const long t64 = (long)cdiv(M, 64) * cdiv(N, 64);
   // (128x128 tiles for the 1024x3072 GRU products -- 192 tiles -- measured neutral in the step: 29.65 vs 29.72 ms)
   const bool big = smp.q ? false : (g_planes_force_tile ? g_planes_force_tile == 2 : t64 >= 2048);
-  if (big && !g_planes_force_tile && !g_planes_nosplit) {
+  if (big && !g_planes_force_tile) {
     // wave quantisation: one 128x128 tile per CU at a time, so 1088 tiles (17 x 1024 rows, N = 1024) take five rounds of
     // the 256 CUs -- 206 us against 146 for the 1024 tiles of 16384 rows.  When the last, partial round is small and made of
     // whole row panels, those rows go to a second launch (64x64 tiles for 1024 rows: ~14 us).
@@ -1829,22 +1767,17 @@ static int gemm_h2_impl(const uint16_t* a0, long a0_ld, long a0_plane, const flo
       const float* bs = seg ? nullptr : bias;
       const int acc = seg ? 1 : accumulate;
       log_launch("h2/128", M, N, sg.k, kk_bytes(M, N, sg.k));
-      route(!hl_on() ? GENRL_ROUTE_128_PLAIN : use_wide(N) ? GENRL_ROUTE_128_HLW : GENRL_ROUTE_128_HL);      // (the default chain's kernel; the experiments' variants report it too)
-#ifdef PLANES_EXPERIMENTS
-      if (g_planes_variant == 1 || g_planes_variant == 6)
-        gemm_planes_kernel<2, 2, 64, 2, 1, 2, false, false, 2><<<tm * tn, 256, 0, (hipStream_t)stream>>>(sg, none, C, ldc, bs, M, N, acc, tm, tn,
-                                                                                           xcd_split(tm, tn), SampleEpi{}, ConvGather{}, LnEpi{});
-      else if (g_planes_variant == 2 || g_planes_variant == 3)
-        gemm_planes_kernel<2, 2, 64, 2, 1, 2, false, false, 4><<<tm * tn, 256, 0, (hipStream_t)stream>>>(sg, none, C, ldc, bs, M, N, acc, tm, tn,
-                                                                                           xcd_split(tm, tn), SampleEpi{}, ConvGather{}, LnEpi{});
-      else
-#endif
+      route(!hl_on() ? GENRL_ROUTE_128_PLAIN : use_wide(N) ? GENRL_ROUTE_128_HLW : GENRL_ROUTE_128_HL);
       if (hl_on() && use_wide(N)) {
         const int tw = cdiv(N, 192);
         gemm_planes_hlw_kernel<false, 3><<<tm * tw, 256, 0, (hipStream_t)stream>>>(sg, C, ldc, bs, M, N, acc, tm, tw, xcd_split(tm, tw), ConvGather{});
-      } else if (hl_on())
-        gemm_planes_hl_kernel<false><<<tm * tn, 256, 0, (hipStream_t)stream>>>(sg, C, ldc, bs, M, N, acc, tm, tn, xcd_split(tm, tn) | (hl_order() << 8), ConvGather{});
-      else
+      } else if (hl_on()) {
+        // tile order 1 (bits 8+ of xcd_m): an XCD walks its sub-block in rounds of 8 row panels x 4 column panels in snake order --
+        // 16384 x 1024 x 1024 122.2 -> 116.8 us, 16384 x 1536 x 1024 180.2 -> 164.8, K = 2048 202.3 -> 197.0 against 0 = row-major over
+        // the sub-block (rounds of 4 x 8); the L2-miss bytes do NOT change (201.8 MB per launch either way = the compulsory 6 MB per round
+        // of 32 resident tiles: no operand survives from one round to the next in a 4 MiB L2), profiles/r05_hl_order.txt
+        gemm_planes_hl_kernel<false><<<tm * tn, 256, 0, (hipStream_t)stream>>>(sg, C, ldc, bs, M, N, acc, tm, tn, xcd_split(tm, tn) | (1 << 8), ConvGather{});
+      } else
         gemm_planes_kernel<2, 2, 64, 2, 1, 2, false><<<tm * tn, 256, 0, (hipStream_t)stream>>>(sg, none, C, ldc, bs, M, N, acc, tm, tn,
                                                                                            xcd_split(tm, tn), SampleEpi{}, ConvGather{}, LnEpi{});
       GENRL_CHECK_LAUNCH();
@@ -1854,18 +1787,8 @@ static int gemm_h2_impl(const uint16_t* a0, long a0_ld, long a0_plane, const flo
     // three 32 KiB stages (96 KiB): a fourth stage measured +0.6 ms on the whole step (28.86 vs 28.2 ms) -- with 128 KiB
     // taken, the other streams' small kernels (32 KiB weight-streaming workgroups) cannot share a CU with this one
     log_launch("h2/64", M, N, k0 + k1, kk_bytes(M, N, k0 + k1));
-#define L64(NS_, PF_) gemm_planes_kernel<1, 1, 64, 3, 1, NS_, true, false, PF_><<<tm * tn, 256, 0, (hipStream_t)stream>>>( \
+#define L64(NS_) gemm_planes_kernel<1, 1, 64, 3, 1, NS_, true><<<tm * tn, 256, 0, (hipStream_t)stream>>>( \
     s0, s1, C, ldc, bias, M, N, accumulate, tm, tn, xcd_split(tm, tn), smp, ConvGather{}, LnEpi{})
-#ifdef PLANES_EXPERIMENTS      /* ring depth / L2 prefetch variants for scripts/cold_bench.py (hipcc -DPLANES_EXPERIMENTS) */
-    switch (g_planes_variant) {
-      case 1: L64(3, 3); break;
-      case 2: L64(3, 6); break;
-      case 3: L64(3, 10); break;
-      case 4: L64(4, 0); break;
-      case 6: L64(2, 6); break;
-      default: L64(3, 0);
-    }
-#else
     // 257 .. 512 tiles (3200-row products of the 512-wide Dreamer-v3 rollout: 400 tiles): two co-resident workgroups per CU on a
     // two-stage ring instead of two rounds of one (GENRL_PLANES_2PER=0 / 1: never / always -- experiments)
     static const char* two_env = getenv("GENRL_PLANES_2PER");
@@ -1875,9 +1798,8 @@ static int gemm_h2_impl(const uint16_t* a0, long a0_ld, long a0_plane, const flo
     // shallow for long K loops on its own): from 257 tiles up while K <= 1536
     const bool two = two_env ? two_env[0] == '1' : (ntile > 256 && k0 + k1 <= 1536);
     route(smp.q ? GENRL_ROUTE_64_SAMPLE : (two ? GENRL_ROUTE_64_NS2 : GENRL_ROUTE_64_NS3));
-    if (two && !smp.q) L64(2, 0);
-    else L64(3, 0);
-#endif
+    if (two && !smp.q) L64(2);
+    else L64(3);
 #undef L64
   }
   GENRL_CHECK_LAUNCH();

@@ -250,9 +250,6 @@ __global__ __launch_bounds__(256, 1) void gemm_planes_tn_kernel(TnArgs g) {
     --left; --fleft;
   };
   auto issue_one = [&](int buf, int i) __attribute__((always_inline)) {
-#if defined(TN_ABL_DMA)      /* ablations (scripts/tn_abl.sh): 1 no tile DMAs in the loop, 2 none of B's, 3 none of A's (wrong results) */
-    if (!first && left < nk - 2 && (TN_ABL_DMA == 1 || (TN_ABL_DMA == 2 && isB) || (TN_ABL_DMA == 3 && !isB))) return;
-#endif
     if (i < NPD) {
       if constexpr (CONVB) {
         if (isB) { tn_glds16(gbase + (size_t)(ro[buf][i] + tapoff), piece0 + buf * STAGE + i * 1024); return; }
@@ -338,9 +335,7 @@ __global__ __launch_bounds__(256, 1) void gemm_planes_tn_kernel(TnArgs g) {
     mfma_one(set, 0);
     mfma_one(set, 1);
     __builtin_amdgcn_sched_barrier(0);
-#ifndef TN_ABL_NOWAIT      /* ablation (scripts/tn_conv_probe.py): do not wait for the stage's DMAs -- wrong results, the MFMA / LDS rate alone */
     tn_wait_vm<0>();
-#endif
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     // (CONVB: this iteration issues stage t+2 with the row offsets of set t % 2, loaded during iteration t-1; the ones of stage

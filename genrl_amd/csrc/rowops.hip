@@ -8,12 +8,6 @@
 #include <algorithm>
 
 #include <cstdlib>
-static const bool WAVE_LN = true;   // wave-per-row LayerNorm kernels for rows of 256 .. 1024 floats
-#ifdef GENRL_NO_NARROW_LN
-#define NARROW_LN false
-#else
-#define NARROW_LN true
-#endif
 
 namespace {
 
@@ -286,9 +280,9 @@ __global__ void reduce_chunks2_kernel(const float* __restrict__ part, float* __r
   float* o = j < N ? out0 + j : (j < 2 * N ? out1 + (j - N) : out2 + (j - 2 * N));
   *o = accumulate ? *o + s : s;
 }
-#ifndef REDUCE2M_MAX
-#define REDUCE2M_MAX 1024  /* partial rows summed by ONE launch of reduce_chunks2m (512 = every block-per-row backward, 1024 = the channel LayerNorm's) */
-#endif
+// partial rows summed by ONE launch of reduce_chunks2m (512 = every block-per-row backward, 1024 = the channel LayerNorm's,
+// narrow_grid_cap())
+constexpr int REDUCE2M_MAX = 1024;
 // one-launch version for a moderate number of partial rows (17..REDUCE2M_MAX): 64 columns x 4 interleaved row
 // subsets per block, summed through LDS (fixed order)
 __global__ __launch_bounds__(256) void reduce_chunks2m_kernel(const float* __restrict__ part, float* __restrict__ out0,
@@ -1401,7 +1395,7 @@ static int ln_act_fwd_impl(const float* x, long ldx, const float* gamma, const f
   const bool fast = N > 256 && N <= 4096 && (N & 3) == 0 && (ldx & 3) == 0 && (ldy & 3) == 0 && aligned16(x) &&
                     aligned16(y) && aligned16(gamma) && aligned16(beta);
   const bool narrow = N <= 256 && (N & 3) == 0 && (ldx & 3) == 0 && (ldy & 3) == 0 && aligned16(x) && aligned16(y) &&
-                      aligned16(gamma) && aligned16(beta) && M >= 64 && NARROW_LN;
+                      aligned16(gamma) && aligned16(beta) && M >= 64;
   // (planes only: the kernels that write planes themselves -- wave- / block-per-row, and the channel kernel's uniform planes)
   if (!y && !(xo.p && (uniform ? narrow : fast))) return GENRL_EINVAL;
   if (narrow) {
@@ -1414,7 +1408,7 @@ static int ln_act_fwd_impl(const float* x, long ldx, const float* gamma, const f
     if (uniform) { GENRL_CHECK_LAUNCH(); return GENRL_OK; }
   } else if (uniform) {
     return GENRL_EINVAL;                           // (uniform planes: the channel-LayerNorm kernel only)
-  } else if (fast && N <= 1024 && WAVE_LN) {
+  } else if (fast && N <= 1024) {
     const int grid = (int)std::min<long>(cdiv(M, 4), 4 * BLK_GRID);
     const int nv = cdiv(N, 256);
 #define GO(NV) hipLaunchKernelGGL((ln_act_fwd_wave_kernel<NV>), dim3(grid), dim3(256), 0, s, x, ldx, gamma, beta, y, ldy, mean, rstd, M, N, eps, act, xo)
@@ -1494,12 +1488,12 @@ long genrl_ln_ws_floats(int M, int N) {
 int genrl_ln_bwd_parts(int M, int N) {
   if (M <= 0 || (N & 3)) return 0;
   if (N <= 256) {
-    if (!(M >= 64 && NARROW_LN)) return 0;
+    if (M < 64) return 0;
     const int gl = N <= 64 ? 16 : (N <= 128 ? 32 : 64);
     return narrow_grid_for(M, gl);
   }
   if (N > 4096) return 0;
-  if (N <= 1024 && WAVE_LN) return blk_grid_for(cdiv(M, 4));
+  if (N <= 1024) return blk_grid_for(cdiv(M, 4));
   return blk_grid_for(M);
 }
 
@@ -1533,7 +1527,7 @@ static int ln_act_bwd_impl(const float* dy, long lddy, const float* x, long ldx,
                      int accumulate_params, PlaneOut xo, void* stream, float* amax_ws = nullptr) {
   GENRL_ENTER();
   if (M <= 0) return GENRL_OK;
-  if (amax_ws && !(N <= 256 && M >= 64 && NARROW_LN)) return GENRL_EINVAL;      // (uniform planes: the channel-LayerNorm kernel only)
+  if (amax_ws && !(N <= 256 && M >= 64)) return GENRL_EINVAL;      // (uniform planes: the channel-LayerNorm kernel only)
   if (xo.p && (!xo.inv || (xo.ld & 3) || xo.ld < N)) return GENRL_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const bool fast = N > 256 && N <= 4096 && (N & 3) == 0 && (lddy & 3) == 0 && (ldx & 3) == 0 &&
@@ -1541,7 +1535,7 @@ static int ln_act_bwd_impl(const float* dy, long lddy, const float* x, long ldx,
                     aligned16(gamma) && aligned16(beta) && (!dgamma || aligned16(ws));
   const bool narrow = N <= 256 && (N & 3) == 0 && (lddy & 3) == 0 && (ldx & 3) == 0 &&
                       (!dx || ((lddx & 3) == 0 && aligned16(dx))) && aligned16(dy) && aligned16(x) && aligned16(gamma) &&
-                      aligned16(beta) && (!dgamma || aligned16(ws)) && M >= 64 && (dgamma || !dcolsum) && NARROW_LN;
+                      aligned16(beta) && (!dgamma || aligned16(ws)) && M >= 64 && (dgamma || !dcolsum);
   if (xo.p && !dx && !(fast && !narrow)) return GENRL_EINVAL;   // (planes without the fp32 copy: the kernels that write planes themselves)
   // accumulate_params & 4: the caller reduces the partial rows itself, later and together with others (genrl_reduce_params_batch;
   // genrl_ln_bwd_parts says how many rows there are) -- only the kernels that leave per-workgroup partials can do that
@@ -1561,7 +1555,7 @@ static int ln_act_bwd_impl(const float* dy, long lddy, const float* x, long ldx,
     if (amax_ws) return xo.p ? split_h2u_from_parts(dx, lddx, M, N, xo, amax_ws, grid, stream) : GENRL_EINVAL;
     return xo.p ? split_after(dx, lddx, M, N, xo, stream) : GENRL_OK;
   }
-  if (fast && N <= 1024 && WAVE_LN) {
+  if (fast && N <= 1024) {
     const int grid = blk_grid_for(cdiv(M, 4));
     const int nv = cdiv(N, 256);
     float* part = dgamma ? ws : nullptr;

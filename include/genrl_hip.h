@@ -344,7 +344,6 @@ int genrl_gemm_x3(const uint16_t* a0, long a0_ld, long a0_plane, const uint16_t*
                   const uint16_t* a1, long a1_ld, long a1_plane, const uint16_t* b1, long b1_ld, long b1_plane, int k1,
                   float* C, long ldc, const float* bias, int M, int N, int accumulate, void* stream);
 int genrl_planes_force_tile(int t);      /* experiments: 0 auto, 1 64x64 tiles, 2 128x128 tiles (both formats) */
-int genrl_planes_variant(int v);         /* experiments: ring depth / L2 prefetch distance of the plane kernels (scripts/cold_bench.py) */
 /* kernel instantiations the most recent plane product entry call (genrl_gemm_h2, _sample, _ln, _conv, _subpixel, _tn, _tn_conv,
  * genrl_gemm_x3) launched, reset by each such call (a refused call reports none): the GENRL_ROUTE_* bits OR-ed in the low 32 bits
  * -- a row-split product or a two-segment 128-tile product reports both of its launches -- and the split-K count of a TN product

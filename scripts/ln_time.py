@@ -1,4 +1,4 @@
-"""LayerNorm(+SiLU) fwd / bwd kernel time at the model's shapes: python scripts/ln_time.py  (GENRL_NO_WAVE_LN=1 for the block-per-row kernels)"""
+"""LayerNorm(+SiLU) fwd / bwd kernel time at the model's shapes: python scripts/ln_time.py"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -26,4 +26,4 @@ for M in (128, 1024, 16384):
     P = _pl.Planes(M, N, dev)
     fp = timeit(lambda: check(L.genrl_ln_act_fwd_h2(x.data_ptr(), N, g.data_ptr(), b.data_ptr(), y.data_ptr(), N, mean.data_ptr(), rstd.data_ptr(), M, N, 1e-5, 1, P.ptr(), P.ld, P.plane, P.inv_ptr(), st), 'fp'))
     out.append(f'M={M}: fwd {f:.1f} fwd+planes {fp:.1f} bwd+params {bw:.1f} bwd {bn:.1f} us')
-print(os.environ.get('GENRL_NO_WAVE_LN', 'wave'), ' | '.join(out))
+print(' | '.join(out))

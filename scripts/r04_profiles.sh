@@ -27,9 +27,8 @@ timeout 900 python bench.py --full --config c4 --no-cpu-baseline > $O/bench_c4.j
 # (5) per-phase kernels of one eager single-stream step
 timeout 300 bash scripts/phase_prof.sh 32 14 > $O/phase_b32.txt 2>&1
 timeout 300 bash scripts/phase_prof.sh 4 14 > $O/phase_b4.txt 2>&1
-# (6) micro-benchmarks: weight-gradient kernel (XCD-aware order), the 64x64 tile's ablations
+# (6) micro-benchmarks: weight-gradient kernel (XCD-aware order)
 timeout 200 python scripts/tn_bench.py > $O/tn_bench.txt 2>&1
-# (the 64x64 tile's ablations need the -DPLANES_ABL builds: scripts/build_abl.sh 1 2 3 4, then scripts/abl64.py -- profiles/r04_abl64.txt)
 timeout 200 python scripts/fused_small_time.py > $O/fused_small_time.txt 2>&1
 timeout 200 python scripts/convt_direct_time.py > $O/convt_direct_time.txt 2>&1
 # (7) in-step time of the plane GEMM per shape; PMC passes; the full default bench line (with CPU baseline and traffic)

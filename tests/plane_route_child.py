@@ -27,7 +27,7 @@ for _p in (os.path.dirname(HERE), HERE):
 from f64check import PAD, U, out_buf, untouched_ok as outside_ok  # noqa: E402
 
 EINVAL = 1
-SWITCHES = ('GENRL_GEMM_LOG', 'GENRL_PLANES_HL', 'GENRL_HL_WIDE', 'GENRL_PLANES_2PER', 'GENRL_PLANES_NOSPLIT')
+SWITCHES = ('GENRL_GEMM_LOG', 'GENRL_PLANES_HL', 'GENRL_HL_WIDE', 'GENRL_PLANES_2PER')
 ROUTE_BITS = {'64/ns3': 0x1, '64/ns2': 0x2, '64/sample': 0x4, '64/ln': 0x8, '128/plain': 0x10, '128/hl': 0x20, '128/hlw': 0x40,
               'conv/plain': 0x80, 'conv/hl': 0x100, 'conv/hlw': 0x200, 'conv/tall96': 0x400, 'subpixel/hl': 0x800,
               'subpixel/hlw': 0x1000, 'x3/64': 0x2000, 'x3/128': 0x4000, 'tn': 0x8000, 'tn/conv': 0x10000}
