@@ -13,6 +13,7 @@ gemm_profile = None      # set to a list to record (M, N, K, start_event, end_ev
 
 
 from .streams import raw_current_stream as _stream      # raw hipStream_t of torch's current stream (private fast call, public fallback)
+from .streams import timed_start, timed_end
 
 
 def _p(t):
@@ -150,6 +151,42 @@ def _grad_buf(p):
     return None
 
 
+def _wgrad_target(W):
+    """where the weight-gradient GEMMs of W (a contiguous fp32 weight on the device of the launch) write -> (tensor, accumulate flag,
+    what the node returns to autograd): W's flat gradient buffer, added into (autograd gets None), or a fresh tensor of W's shape
+    that is returned"""
+    tgt = _grad_buf(W)
+    if tgt is not None:
+        return tgt, True, None
+    dW = torch.empty(W.shape, device=W.device)
+    return dW, False, dW
+
+
+def _bias_grad(b, x2d, ld=None):
+    """gradient of the bias b = column sums of x2d (row spacing ld): added into b's flat gradient buffer (-> None) or returned"""
+    tgt = _grad_buf(b)
+    if tgt is None:
+        return colsum(x2d, ld=ld)
+    colsum(x2d, out=tgt, accumulate=True, ld=ld)
+    return None
+
+
+def _ln_param_targets(M, N, gamma, beta, bias, dev, need=True, bias_optional=False):
+    """where a LayerNorm backward over M rows of width N puts dgamma, dbeta and the column sums of dx (the producing layer's bias
+    gradient) -> (g0, g1, g2, workspace, accumulate_params, direct).  direct: all three have flat gradient buffers and the sums are added
+    into them (their reduction deferred where defer_reduce takes it) -- the node then returns None for them; else three rows of a fresh
+    tensor.  need False (nobody asked for these gradients): nothing is allocated.  bias_optional: a layer WITHOUT bias still goes direct
+    (g2 None); elsewhere a missing bias buffer means not direct"""
+    if not need:
+        return None, None, None, None, 0, False
+    g0, g1, g2 = _grad_buf(gamma), _grad_buf(beta), _grad_buf(bias)
+    direct = g0 is not None and g1 is not None and (g2 is not None or (bias_optional and bias is None))
+    if not direct:
+        g0, g1, g2 = torch.empty(3, N, device=dev).unbind(0)
+    ws = _ws(lib().genrl_ln_ws_floats(M, N), dev)
+    return g0, g1, g2, ws, (1 | defer_reduce(M, N, ws, g0, g1, g2)) if direct else 0, direct
+
+
 class _WgradStream:
     """Weight-gradient GEMMs are off the critical path of backpropagation (nothing downstream in
     the backward pass reads dW) and accumulate into persistent buffers: when enabled they are
@@ -188,37 +225,37 @@ def _ws(n, dev):
 
 # ------------------------------------------------------------------ raw (non-autograd) calls
 
+def _sgemm_tag(M, a_ks, b_ks, conv=''):
+    """tag of a genrl_sgemm launch in bench.py's event pass; asked for AFTER the launch (it names the pipe the dispatcher took)"""
+    route = ('k' if a_ks == 1 else 'r') + ('k' if b_ks == 1 else 'r') + conv
+    return route + ('/skinny' if (M <= 32 and a_ks == 1 and not conv) else f'/pipe{lib().genrl_sgemm_last_pipe()}')
+
+
 def sgemm(A, a_rs, a_ks, B, b_rs, b_ks, C, ldc, bias, M, N, K, accumulate=False, a_off=0, b_off=0, c_off=0):
     """C[m,n] (+)= sum_k A[m*a_rs+k*a_ks] B[n*b_rs+k*b_ks] (+bias[n]); offsets in elements."""
     _on_gpu(A, B, C)
-    if gemm_profile is not None:        # bench.py: HIP events around every launch of the GEMM kernel
-        e0 = torch.cuda.Event(enable_timing=True); e0.record()
+    e0 = timed_start(gemm_profile)
     nws = lib().genrl_sgemm_ws_floats(M, N, K)
     ws = torch.empty(nws, dtype=torch.float32, device=C.device) if nws > 0 else None
     check(lib().genrl_sgemm(A.data_ptr() + 4 * a_off, a_rs, a_ks, B.data_ptr() + 4 * b_off, b_rs, b_ks,
                             C.data_ptr() + 4 * c_off, ldc, _p(bias), M, N, K, int(accumulate), _p(ws), nws,
                             _stream()), 'sgemm')
-    if gemm_profile is not None:
-        e1 = torch.cuda.Event(enable_timing=True); e1.record()
-        gemm_profile.append((M, N, K, e0, e1, ('k' if a_ks == 1 else 'r') + ('k' if b_ks == 1 else 'r') +
-                             ('/skinny' if (M <= 32 and a_ks == 1) else f'/pipe{lib().genrl_sgemm_last_pipe()}')))
+    if e0 is not None:
+        timed_end(gemm_profile, e0, M, N, K, _sgemm_tag(M, a_ks, b_ks))
 
 
 def sgemm_conv(A, a_rs, a_ks, B, b_rs, b_ks, C, ldc, bias, M, N, K, which, img, accumulate=False):
     """sgemm with operand `which` (1 = A, 2 = B) read as the implicit stride-2 patch matrix of the NHWC
     image img = (H, W, C, k) (include/genrl_hip.h: genrl_sgemm_conv) — no materialised im2col."""
     _on_gpu(A, B, C)
-    if gemm_profile is not None:
-        e0 = torch.cuda.Event(enable_timing=True); e0.record()
+    e0 = timed_start(gemm_profile)
     nws = lib().genrl_sgemm_ws_floats(M, N, K)
     ws = torch.empty(nws, dtype=torch.float32, device=C.device) if nws > 0 else None
     H, W, Cc, k = img
     check(lib().genrl_sgemm_conv(A.data_ptr(), a_rs, a_ks, B.data_ptr(), b_rs, b_ks, C.data_ptr(), ldc, _p(bias),
                                  M, N, K, int(accumulate), _p(ws), nws, which, H, W, Cc, k, _stream()), 'sgemm_conv')
-    if gemm_profile is not None:
-        e1 = torch.cuda.Event(enable_timing=True); e1.record()
-        gemm_profile.append((M, N, K, e0, e1, ('k' if a_ks == 1 else 'r') + ('k' if b_ks == 1 else 'r') +
-                             f'/conv{which}/pipe{lib().genrl_sgemm_last_pipe()}'))
+    if e0 is not None:
+        timed_end(gemm_profile, e0, M, N, K, _sgemm_tag(M, a_ks, b_ks, f'/conv{which}'))
 
 
 def colsum(x2d, out=None, accumulate=False, ld=None):
@@ -316,18 +353,14 @@ class _Linear(Function):
             sgemm(dy2, ldy, 1, W, 1, K, dx, K, None, M, K, N)          # dx = dy W
             dx = dx.reshape(ctx.xshape)
         if ctx.needs_input_grad[1]:
-            tgt = _grad_buf(W)
-            if tgt is not None:
-                wgrad_stream.run(lambda: sgemm(dy2, 1, ldy, x2, 1, K, tgt, K, None, N, K, M, accumulate=True), dy2, x2)
+            tgt, acc, dW = _wgrad_target(W)
+            wg = lambda: sgemm(dy2, 1, ldy, x2, 1, K, tgt, K, None, N, K, M, accumulate=acc)     # dW = dy^T x
+            if acc:
+                wgrad_stream.run(wg, dy2, x2)
             else:
-                dW = torch.empty(N, K, device=dy.device)
-                sgemm(dy2, 1, ldy, x2, 1, K, dW, K, None, N, K, M)     # dW = dy^T x
+                wg()
         if ctx.has_bias and ctx.needs_input_grad[2]:
-            tgt = _grad_buf(ctx.bias)
-            if tgt is not None:
-                colsum(dy2, out=tgt, accumulate=True, ld=ldy)
-            else:
-                db = colsum(dy2, ld=ldy)
+            db = _bias_grad(ctx.bias, dy2, ldy)
         return dx, dW, db
 
 
@@ -944,16 +977,9 @@ class ActorTape:
                     copy2d(dWh, U, bufs[2 * i], U, A, U, None, True, src_off=i * A * U)
                     copy2d(dbh, A2, bufs[2 * i + 1], A, 1, A, None, True, src_off=i * A)
                 return None, None
-        tgt = _grad_buf(self.head_w)
-        dWh = None if tgt is not None else torch.empty(A2, U, device=dev)
-        sgemm(d, 1, A2, x_last, 1, U, tgt if tgt is not None else dWh, U, None, A2, U, M, accumulate=tgt is not None)
-        tb = _grad_buf(self.head_b)
-        dbh = None
-        if tb is not None:
-            colsum(d, out=tb, accumulate=True)
-        else:
-            dbh = colsum(d)
-        return dWh, dbh
+        tgt, acc, dWh = _wgrad_target(self.head_w)
+        sgemm(d, 1, A2, x_last, 1, U, tgt, U, None, A2, U, M, accumulate=acc)
+        return dWh, _bias_grad(self.head_b, d)
 
     def step(self, t, x1, x2):
         flat = [q for l in self.layers for q in l[:4]]
@@ -1015,34 +1041,23 @@ class ActorTape:
             W, b, gamma, beta, eps = self.layers[l]
             U, K = W.shape
             dpre = torch.empty(M, U, device=dev)
-            tg, tbe, tc = _grad_buf(gamma), _grad_buf(beta), (_grad_buf(b) if b is not None else None)
-            direct = tg is not None and tbe is not None and (b is None or tc is not None)
-            if direct:
-                g0, g1, g2, acc_p = tg, tbe, tc, 1
-            else:
-                gb = torch.empty(3, U, device=dev)
-                g0, g1, g2, acc_p = gb[0], gb[1], gb[2], 0
-            ws = _ws(lib().genrl_ln_ws_floats(M, U), dev)
-            if direct:
-                acc_p |= defer_reduce(M, U, ws, g0, g1, g2)
+            g0, g1, g2, ws, acc_p, direct = _ln_param_targets(M, U, gamma, beta, b, dev, bias_optional=True)
             check(lib().genrl_ln_act_bwd(_p(dy), U, _p(self.pre[l]), U, _p(gamma), _p(beta), _p(self.mean[l]),
                                          _p(self.rstd[l]), _p(dpre), U, _p(g0), _p(g1), _p(g2), _p(ws), M, U, 1, acc_p,
                                          _stream()), 'ln_act_bwd')
-            tw = _grad_buf(W)
-            acc = tw is not None
-            dW = tw if acc else torch.empty(U, K, device=dev)
+            tw, acc, dW = _wgrad_target(W)
             if l > 0:
                 x = self.y[l - 1]
-                sgemm(dpre, 1, U, x, 1, K, dW, K, None, U, K, M, accumulate=acc)
+                sgemm(dpre, 1, U, x, 1, K, tw, K, None, U, K, M, accumulate=acc)
                 dy = torch.empty(M, K, device=dev)
                 sgemm(dpre, U, 1, W, 1, K, dy, K, None, M, K, U)
             else:
                 x1, x2 = self.inputs
                 K1, K2 = x1.shape[-1], x2.shape[-1]
                 assert x1.is_contiguous() and x2.is_contiguous() and x1.shape[0] >= H and K1 + K2 == K
-                sgemm(dpre, 1, U, x1, 1, K1, dW, K, None, U, K1, M, accumulate=acc)
-                sgemm(dpre, 1, U, x2, 1, K2, dW, K, None, U, K2, M, c_off=K1, accumulate=acc)
-            grads[l] = (None if acc else dW, None if (direct or b is None) else g2, None if direct else g0,
+                sgemm(dpre, 1, U, x1, 1, K1, tw, K, None, U, K1, M, accumulate=acc)
+                sgemm(dpre, 1, U, x2, 1, K2, tw, K, None, U, K2, M, c_off=K1, accumulate=acc)
+            grads[l] = (dW, None if (direct or b is None) else g2, None if direct else g0,
                         None if direct else g1)
         return dWh, dbh, grads
 
@@ -1264,15 +1279,7 @@ def _ln_bwd_rows(dy2d, pre2d, gamma, beta, mean, rstd, bias=None):
     returned as None (nothing left for autograd to add)."""
     M, N = pre2d.shape
     dpre = torch.empty_like(pre2d)
-    tg, tb, tc = _grad_buf(gamma), _grad_buf(beta), _grad_buf(bias)
-    direct = tg is not None and tb is not None and tc is not None
-    if direct:
-        g0, g1, g2 = tg, tb, tc
-    else:
-        gb = torch.empty(3, N, device=pre2d.device)
-        g0, g1, g2 = gb[0], gb[1], gb[2]
-    ws = _ws(lib().genrl_ln_ws_floats(M, N), pre2d.device)
-    acc_p = int(direct) | (defer_reduce(M, N, ws, g0, g1, g2) if direct else 0)
+    g0, g1, g2, ws, acc_p, direct = _ln_param_targets(M, N, gamma, beta, bias, pre2d.device)
     check(lib().genrl_ln_act_bwd(_p(dy2d), N, _p(pre2d), N, _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dpre), N,
                                  _p(g0), _p(g1), _p(g2), _p(ws), M, N, 1, acc_p, _stream()), 'ln_act_bwd')
     return (dpre, None, None, None) if direct else (dpre, g0, g1, g2)
@@ -1413,13 +1420,10 @@ class _ConvT2dS2(Function):
             # the 3-channel end of the decoder: gather form on the fp32 matrix cores, no cols matrix (genrl_convt_small_co_fwd)
             Ho, Wo = 2 * (Hi - 1) + k, 2 * (Wi - 1) + k
             y = torch.empty((Nimg, Co, Ho, Wo) if out_nchw else (Nimg, Ho, Wo, Co), device=x.device)
-            if gemm_profile is not None:
-                e0 = torch.cuda.Event(enable_timing=True); e0.record()
+            e0 = timed_start(gemm_profile)
             check(lib().genrl_convt_small_co_fwd(_p(x), _p(Wp), _p(b), _p(y), Nimg, Hi, Wi, Ci, Co, k, int(out_nchw), _stream()),
                   'convt_small_co_fwd')
-            if gemm_profile is not None:
-                e1 = torch.cuda.Event(enable_timing=True); e1.record()
-                gemm_profile.append((Nimg * (Hi + 2) * (Wi + 2), 4 * Co, 9 * Ci, e0, e1, 'kk/convt_direct'))
+            timed_end(gemm_profile, e0, Nimg * (Hi + 2) * (Wi + 2), 4 * Co, 9 * Ci, 'kk/convt_direct')
         else:
             cols = torch.empty(M, Nw, device=x.device)
             sgemm(x, Ci, 1, Wp, 1, Nw, cols, Nw, None, M, Nw, Ci)         # cols = x W
@@ -1458,13 +1462,10 @@ class _ConvT2dS2(Function):
             if ctx.needs_input_grad[1]:
                 dW = torch.empty(Ci, Nw, device=dy.device)
                 ws = torch.empty(lib().genrl_convt_small_co_bwd_ws_floats(Ci, Co), device=dy.device)
-            if gemm_profile is not None:
-                e0 = torch.cuda.Event(enable_timing=True); e0.record()
+            e0 = timed_start(gemm_profile)
             check(lib().genrl_convt_small_co_bwd(_p(x), _p(Wp), _p(dy), _p(dx), _p(dW), _p(ws), Nimg, Hi, Wi, Ci, Co, k, _stream()),
                   'convt_small_co_bwd')
-            if gemm_profile is not None:
-                e1 = torch.cuda.Event(enable_timing=True); e1.record()
-                gemm_profile.append((M, Ci, Nw, e0, e1, 'kk/convt_direct_bwd'))
+            timed_end(gemm_profile, e0, M, Ci, Nw, 'kk/convt_direct_bwd')
             if ctx.needs_input_grad[2]:
                 db = _nchw_bias_grad(dy, ctx.bias)
             return dx, dW, db, None, None, None, None, None
@@ -1639,10 +1640,7 @@ class _GRUStep(Function):
         else:
             dh = None
         if ctx.needs_input_grad[2]:
-            tgt = _grad_buf(W)
-            acc = tgt is not None
-            if not acc:
-                dW = tgt = torch.empty(3 * D, K, device=h.device)
+            tgt, acc, dW = _wgrad_target(W)
             def wg():
                 sgemm(dpre, 1, 3 * D, x, 1, I, tgt, K, None, 3 * D, I, R, accumulate=acc)
                 sgemm(dpre, 1, 3 * D, h, 1, D, tgt, K, None, 3 * D, D, R, accumulate=acc, c_off=I)
@@ -1774,23 +1772,18 @@ class _GRUSeq(Function):
             dx = torch.empty_like(x)
             sgemm(dpre, 3 * D, 1, W, 1, K, dx, I, None, T * B, I, 3 * D)
         if ctx.needs_input_grad[3]:
-            tw = _grad_buf(W)
-            acc = tw is not None
-            dW = tw if acc else torch.empty(3 * D, K, device=dev)
-            sgemm(dpre, 1, 3 * D, x, 1, I, dW, K, None, 3 * D, I, T * B, accumulate=acc)
+            tw, acc, dW = _wgrad_target(W)
+            sgemm(dpre, 1, 3 * D, x, 1, I, tw, K, None, 3 * D, I, T * B, accumulate=acc)
             if ctx.has_mask:
-                sgemm(dpre, 1, 3 * D, hm, 1, D, dW, K, None, 3 * D, D, T * B, c_off=I, accumulate=acc)
+                sgemm(dpre, 1, 3 * D, hm, 1, D, tw, K, None, 3 * D, D, T * B, c_off=I, accumulate=acc)
             else:   # h_{t-1} = [h0, out[:-1]]
-                sgemm(dpre, 1, 3 * D, h0, 1, D, dW, K, None, 3 * D, D, B, c_off=I, accumulate=acc)
+                sgemm(dpre, 1, 3 * D, h0, 1, D, tw, K, None, 3 * D, D, B, c_off=I, accumulate=acc)
                 if T > 1:
-                    ws2 = dW.new_empty(0)
                     nws = lib().genrl_sgemm_ws_floats(3 * D, D, (T - 1) * B)
                     ws2 = torch.empty(nws, device=dev) if nws > 0 else None
                     check(lib().genrl_sgemm(dpre.data_ptr() + 4 * B3D, 1, 3 * D, out.data_ptr(), 1, D,
-                                            dW.data_ptr() + 4 * I, K, None, 3 * D, D, (T - 1) * B, 1, _p(ws2), nws,
+                                            tw.data_ptr() + 4 * I, K, None, 3 * D, D, (T - 1) * B, 1, _p(ws2), nws,
                                             _stream()), 'sgemm')
-            if acc:
-                dW = None
         if ctx.needs_input_grad[2]:
             dh0 = nxt * mask[0].unsqueeze(-1) if ctx.has_mask else nxt.clone()
         return (dx, None, dh0, dW, None, None) if direct else (dx, None, dh0, dW, gb[0], gb[1])
@@ -1840,18 +1833,7 @@ class _DenseLNAct(Function):
         dy2 = dy.reshape(M, N).contiguous()
         dpre = torch.empty_like(pre)          # gradient w.r.t. the pre-LayerNorm projection
         need_p = ctx.needs_input_grad[2] or ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
-        tg, tb, tc = _grad_buf(gamma), _grad_buf(beta), (_grad_buf(ctx.bias) if ctx.has_bias else None)
-        direct = need_p and tg is not None and tb is not None and tc is not None
-        if direct:
-            g0, g1, g2, acc_p = tg, tb, tc, 1
-        elif need_p:
-            gb = torch.empty(3, N, device=dev)
-            g0, g1, g2, acc_p = gb[0], gb[1], gb[2], 0
-        else:
-            g0 = g1 = g2 = None; acc_p = 0
-        ws = _ws(lib().genrl_ln_ws_floats(M, N), dev) if need_p else None
-        if direct:
-            acc_p |= defer_reduce(M, N, ws, g0, g1, g2)
+        g0, g1, g2, ws, acc_p, direct = _ln_param_targets(M, N, gamma, beta, ctx.bias, dev, need=need_p)
         check(lib().genrl_ln_act_bwd(_p(dy2), N, _p(pre), N, _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dpre), N,
                                      _p(g0), _p(g1), _p(g2), _p(ws), M, N, 1, acc_p, _stream()), 'ln_act_bwd')
         d1 = d2 = dW = None
@@ -1864,10 +1846,7 @@ class _DenseLNAct(Function):
             sgemm(dpre, N, 1, W, 1, K, d2, K2, None, M, K2, N, b_off=K1)
             d2 = d2.reshape(ctx.shapes[1])
         if ctx.needs_input_grad[2]:
-            tgt = _grad_buf(W)
-            acc = tgt is not None
-            if not acc:
-                dW = tgt = torch.empty(N, K, device=dev)
+            tgt, acc, dW = _wgrad_target(W)
             def wg():
                 sgemm(dpre, 1, N, a, 1, K1, tgt, K, None, N, K1, M, accumulate=acc)
                 if ctx.has2:
@@ -1901,15 +1880,39 @@ class _ObserveArgs(ctypes.Structure):          # genrl_observe (include/genrl_hi
                 + [('direct', _CI)])
 
 
+def _observe_args(dims, eps, W_in, W_g, W_o, W_d, params, bufs, stats, **extra):
+    """the _ObserveArgs that _ObserveSeq's forward and backward and rssm_imagine_seq share -> (args, w_s, ws): the latent block of W_in
+    the scan reads and its GEMM workspace, both to be kept alive over the call.  W_in: the (U, S K + A) weight, or the w_s of an earlier
+    call; params = (in_g, in_be, gru_g, gru_be, out_g, out_be, dist_b), bufs = (sm, xpre, xh, gpre, deter, opre, o, plog), stats (6, T, B);
+    extra: the pointer fields that differ (mask, q, pst, out_b, the backward's own).  opre_acc and the ping-pong pairs are the caller's."""
+    T, B, S, K, D, U = dims
+    SK, Kin = S * K, W_in.shape[1]
+    if Kin % 4:          # the latent block of _img_in, rows 16-byte aligned (SK + A is not a multiple of 4 with 6 or 10 actions)
+        w_s = torch.empty(U, SK, device=W_in.device)
+        copy2d(W_in, Kin, w_s, SK, U, SK)
+    else:
+        w_s = W_in
+    a = _ObserveArgs()
+    a.T, a.B, a.S, a.K, a.D, a.U = dims
+    a.unimix, a.in_eps, a.out_eps = UNIMIX, eps[0], eps[1]
+    a.w_in_s, a.ld_in_s, a.w_g, a.ld_g, a.w_o, a.ld_o, a.w_d = _p(w_s), w_s.shape[1], _p(W_g), U + D, _p(W_o), W_o.shape[1], _p(W_d)
+    names = ('in_g', 'in_be', 'gru_g', 'gru_be', 'out_g', 'out_be', 'dist_b', 'sm', 'xpre', 'xh', 'gpre', 'deter', 'opre', 'o', 'plog')
+    for n_, t_ in (*zip(names, (*params, *bufs)), *extra.items()):
+        setattr(a, n_, _p(t_))
+    for i, n_ in enumerate(('xm', 'xr', 'gm', 'gr', 'om', 'orr')):
+        setattr(a, n_, stats[i].data_ptr())
+    nws = max(lib().genrl_sgemm_ws_floats(*s_) for s_ in _observe_shapes(B, SK, U, D))
+    ws = torch.empty(max(nws, 1), device=W_in.device)
+    a.ws, a.ws_floats = ws.data_ptr(), nws
+    return a, w_s, ws
+
+
 def _sgemm_ptr(A, a_rs, a_ks, B, b_rs, b_ks, C, ldc, bias, M, N, K, acc, ws, nws):
     """genrl_sgemm on raw addresses (the Python twins of the C launch loops; timed like sgemm() under bench.py's event pass)"""
-    if gemm_profile is not None:
-        e0 = torch.cuda.Event(enable_timing=True); e0.record()
+    e0 = timed_start(gemm_profile)
     check(lib().genrl_sgemm(A, a_rs, a_ks, B, b_rs, b_ks, C, ldc, bias, M, N, K, int(acc), ws, nws, _stream()), 'sgemm')
-    if gemm_profile is not None:
-        e1 = torch.cuda.Event(enable_timing=True); e1.record()
-        gemm_profile.append((M, N, K, e0, e1, ('k' if a_ks == 1 else 'r') + ('k' if b_ks == 1 else 'r') +
-                             ('/skinny' if (M <= 32 and a_ks == 1) else f'/pipe{lib().genrl_sgemm_last_pipe()}')))
+    if e0 is not None:
+        timed_end(gemm_profile, e0, M, N, K, _sgemm_tag(M, a_ks, b_ks))
 
 
 def _observe_fwd_py(a):
@@ -1982,16 +1985,7 @@ def _ln_params_batched(dy, lddy, pre, gamma, beta, bias, mean, rstd, M, N):
     """dgamma / dbeta / bias gradient of a LayerNorm(+SiLU) layer over all M rows at once (the scan's per-step backward launches ask
     for dx only); added straight into the flat gradient buffers under the Optimizer, else returned as (dgamma, dbeta, dbias)"""
     dev = pre.device
-    tg, tb, tc = _grad_buf(gamma), _grad_buf(beta), _grad_buf(bias)
-    direct = tg is not None and tb is not None and tc is not None
-    if direct:
-        g0, g1, g2, acc_p = tg, tb, tc, 1
-    else:
-        gb = torch.empty(3, N, device=dev)
-        g0, g1, g2, acc_p = gb[0], gb[1], gb[2], 0
-    ws = _ws(lib().genrl_ln_ws_floats(M, N), dev)
-    if direct:
-        acc_p |= defer_reduce(M, N, ws, g0, g1, g2)
+    g0, g1, g2, ws, acc_p, direct = _ln_param_targets(M, N, gamma, beta, bias, dev)
     scratch = torch.empty(M, N, device=dev)
     check(lib().genrl_ln_act_bwd(dy.data_ptr(), lddy, _p(pre), N, _p(gamma), _p(beta), _p(mean), _p(rstd), _p(scratch), N,
                                  _p(g0), _p(g1), _p(g2), _p(ws), M, N, 1, acc_p, _stream()), 'ln_act_bwd')
@@ -2028,37 +2022,19 @@ class _ObserveSeq(Function):
         sgemm(am, A, 1, W_in, Kin, 1, xpre, U, b_in, T * B, U, A, b_off=SK)
         opre = torch.empty(T, B, U, device=dev)
         sgemm(emb, E, 1, W_o, D + E, 1, opre, U, b_o, T * B, U, E, b_off=D)
-        # the latent block of _img_in, rows 16-byte aligned (SK + A is not a multiple of 4 with 6 or 10 actions)
-        if Kin % 4:
-            w_s = torch.empty(U, SK, device=dev)
-            copy2d(W_in, Kin, w_s, SK, U, SK)
-            ld_s = SK
-        else:
-            w_s, ld_s = W_in, Kin
         sm = torch.empty(T, B, SK, device=dev)
-        copy2d(stoch0, SK, sm, SK, B, SK, mask[0])
         xh = torch.empty(T, B, X, device=dev)
-        copy2d(deter0, D, xh, X, B, D, mask[0], dst_off=U)
         gpre = torch.empty(T, B, 3 * D, device=dev)
         deter = torch.empty(T, B, D, device=dev)
         o = torch.empty(T, B, U, device=dev)
         plog = torch.empty(T, B, SK, device=dev)
         pst = torch.empty(T, B, SK, device=dev)
         stats = torch.empty(6, T, B, device=dev)
-        a = _ObserveArgs()
-        a.T, a.B, a.S, a.K, a.D, a.U = T, B, S, K, D, U
-        a.unimix, a.in_eps, a.out_eps = UNIMIX, eps_in, eps_o
-        a.w_in_s, a.ld_in_s, a.w_g, a.ld_g, a.w_o, a.ld_o, a.w_d = _p(w_s), ld_s, _p(W_g), X, _p(W_o), D + E, _p(W_d)
+        a, w_s, ws = _observe_args((T, B, S, K, D, U), (eps_in, eps_o), W_in, W_g, W_o, W_d, (g_in, be_in, g_g, be_g, g_o, be_o, b_d),
+                                   (sm, xpre, xh, gpre, deter, opre, o, plog), stats, mask=mask, q=q, pst=pst)
         a.opre_acc = 1
-        for n_, t_ in (('in_g', g_in), ('in_be', be_in), ('gru_g', g_g), ('gru_be', be_g), ('out_g', g_o), ('out_be', be_o), ('dist_b', b_d),
-                       ('mask', mask), ('q', q), ('sm', sm), ('xpre', xpre), ('xh', xh), ('gpre', gpre), ('deter', deter), ('opre', opre),
-                       ('o', o), ('plog', plog), ('pst', pst)):
-            setattr(a, n_, _p(t_))
-        for i, n_ in enumerate(('xm', 'xr', 'gm', 'gr', 'om', 'orr')):
-            setattr(a, n_, stats[i].data_ptr())
-        nws = max(lib().genrl_sgemm_ws_floats(*s_) for s_ in _observe_shapes(B, SK, U, D))
-        ws = torch.empty(max(nws, 1), device=dev)
-        a.ws, a.ws_floats = ws.data_ptr(), nws
+        copy2d(stoch0, SK, sm, SK, B, SK, mask[0])
+        copy2d(deter0, D, xh, X, B, D, mask[0], dst_off=U)
         keep = _scan_fuse(a, w_s, T, B, S, K, U, dev)
         if SEQ_C and gemm_profile is None:
             check(lib().genrl_observe_seq_fwd(ctypes.byref(a), _stream()), 'observe_seq_fwd')
@@ -2088,23 +2064,12 @@ class _ObserveSeq(Function):
         direct = tg is not None and tb is not None
         gb = (tg, tb) if direct else torch.empty(2, 3 * D, device=dev)
         gws = torch.empty(lib().genrl_gru_ws_floats(B, D), device=dev)
-        a = _ObserveArgs()
-        a.T, a.B, a.S, a.K, a.D, a.U = T, B, S, K, D, U
-        a.unimix, a.in_eps, a.out_eps = UNIMIX, ctx.eps[0], ctx.eps[1]
-        a.w_in_s, a.ld_in_s, a.w_g, a.ld_g, a.w_o, a.ld_o, a.w_d = _p(w_s), w_s.shape[1], _p(W_g), X, _p(W_o), D + E, _p(W_d)
+        a, _, ws = _observe_args((T, B, S, K, D, U), ctx.eps, w_s, W_g, W_o, W_d, (g_in, be_in, g_g, be_g, g_o, be_o, b_d),
+                                 (sm, xpre, xh, gpre, deter, opre, o, plog), stats, mask=mask, q=q, d_pst=d_pst, dlg=dlg, dd=dd, dov=dov,
+                                 dopre=dopre, dgpre=dgpre, dxh=dxh, dxpre=dxpre, dgamma=gb[0], dbeta=gb[1], gws=gws)
         a.opre_acc = 1
-        for n_, t_ in (('in_g', g_in), ('in_be', be_in), ('gru_g', g_g), ('gru_be', be_g), ('out_g', g_o), ('out_be', be_o), ('dist_b', b_d),
-                       ('mask', mask), ('q', q), ('sm', sm), ('xpre', xpre), ('xh', xh), ('gpre', gpre), ('deter', deter), ('opre', opre),
-                       ('o', o), ('plog', plog), ('d_pst', d_pst), ('dlg', dlg), ('dd', dd), ('dov', dov), ('dopre', dopre),
-                       ('dgpre', dgpre), ('dxh', dxh), ('dxpre', dxpre), ('dgamma', gb[0]), ('dbeta', gb[1]), ('gws', gws)):
-            setattr(a, n_, _p(t_))
-        for i, n_ in enumerate(('xm', 'xr', 'gm', 'gr', 'om', 'orr')):
-            setattr(a, n_, stats[i].data_ptr())
         a.dsa, a.dsb, a.dhd_a, a.dhd_b = ds2[0].data_ptr(), ds2[1].data_ptr(), dh2[0].data_ptr(), dh2[1].data_ptr()
         a.direct = int(direct)
-        nws = max(lib().genrl_sgemm_ws_floats(*s_) for s_ in _observe_shapes(B, SK, U, D))
-        ws = torch.empty(max(nws, 1), device=dev)
-        a.ws, a.ws_floats = ws.data_ptr(), nws
         if SEQ_C and gemm_profile is None:
             fin = ctypes.c_int(0)
             check(lib().genrl_observe_seq_bwd(ctypes.byref(a), ctypes.byref(fin), _stream()), 'observe_seq_bwd')
@@ -2117,20 +2082,12 @@ class _ObserveSeq(Function):
             """dP (+)= sum over parts of dY^T X into column blocks: parts = [(dY2d, ldy, N, X2d, ldx, Kx, c_off)]"""
             if P is None:
                 return None
-            tgt = _grad_buf(P)
-            acc = tgt is not None
-            out = tgt if acc else torch.empty_like(P)
+            tgt, acc, dP = _wgrad_target(P)
             for (dy_, ldy_, n_, x_, ldx_, k_, off_) in parts:
-                sgemm(dy_, 1, ldy_, x_, 1, ldx_, out, P.shape[1], None, n_, k_, M, accumulate=acc, c_off=off_)
-            return None if acc else out
+                sgemm(dy_, 1, ldy_, x_, 1, ldx_, tgt, P.shape[1], None, n_, k_, M, accumulate=acc, c_off=off_)
+            return dP
         dW_d = wgrad(W_d if need[17] else None, [(dlg, SK, SK, o, U, U, 0)])
-        db_d = None
-        if need[18]:
-            tgt = _grad_buf(b_d)
-            if tgt is not None:
-                colsum(dlg.reshape(M, SK), out=tgt, accumulate=True)
-            else:
-                db_d = colsum(dlg.reshape(M, SK))
+        db_d = _bias_grad(b_d, dlg.reshape(M, SK)) if need[18] else None
         dg_o, dbe_o, db_o = _ln_params_batched(dov, U, opre, g_o, be_o, b_o, stats[4], stats[5], M, U)
         dW_o = wgrad(W_o if need[13] else None, [(dopre, U, U, deter, D, D, 0), (dopre, U, U, emb, E, E, D)])
         d_emb = None
@@ -2207,16 +2164,8 @@ def rssm_imagine_seq(act, stoch0, deter0, q, S, K, W_in, b_in, g_in, be_in, W_g,
     assert U % 4 == 0 and D % 4 == 0 and SK % 4 == 0 and (q is None or q.numel() == T * B * SK)
     xpre = torch.empty(T, B, U, device=dev)
     sgemm(act, A, 1, W_in, Kin, 1, xpre, U, b_in, T * B, U, A, b_off=SK)
-    if Kin % 4:                                   # the latent block of _img_in with 16-byte aligned rows
-        w_s = torch.empty(U, SK, device=dev)
-        copy2d(W_in, Kin, w_s, SK, U, SK)
-        ld_s = SK
-    else:
-        w_s, ld_s = W_in, Kin
     sm = torch.empty(T, B, SK, device=dev)
-    copy2d(stoch0, SK, sm, SK, B, SK)
     xh = torch.empty(T, B, X, device=dev)
-    copy2d(deter0, D, xh, X, B, D, dst_off=U)
     gpre = torch.empty(T, B, 3 * D, device=dev)
     deter = torch.empty(T, B, D, device=dev)
     opre = torch.empty(T, B, U, device=dev)
@@ -2224,20 +2173,11 @@ def rssm_imagine_seq(act, stoch0, deter0, q, S, K, W_in, b_in, g_in, be_in, W_g,
     plog = torch.empty(T, B, SK, device=dev)
     pst = torch.empty(T, B, SK, device=dev)
     stats = torch.empty(6, T, B, device=dev)
-    a = _ObserveArgs()
-    a.T, a.B, a.S, a.K, a.D, a.U = T, B, S, K, D, U
-    a.unimix, a.in_eps, a.out_eps = UNIMIX, eps_in, eps_out
-    a.w_in_s, a.ld_in_s, a.w_g, a.ld_g, a.w_o, a.ld_o, a.w_d = _p(w_s), ld_s, _p(W_g), X, _p(W_out), D, _p(W_dist)
+    a, w_s, ws = _observe_args((T, B, S, K, D, U), (eps_in, eps_out), W_in, W_g, W_out, W_dist, (g_in, be_in, g_g, be_g, g_out, be_out, b_dist),
+                               (sm, xpre, xh, gpre, deter, opre, o, plog), stats, q=q, pst=pst, out_b=b_out)
     a.opre_acc = 0
-    for n_, t_ in (('in_g', g_in), ('in_be', be_in), ('gru_g', g_g), ('gru_be', be_g), ('out_g', g_out), ('out_be', be_out),
-                   ('dist_b', b_dist), ('out_b', b_out), ('q', q), ('sm', sm), ('xpre', xpre), ('xh', xh), ('gpre', gpre), ('deter', deter),
-                   ('opre', opre), ('o', o), ('plog', plog), ('pst', pst)):
-        setattr(a, n_, _p(t_))
-    for i, n_ in enumerate(('xm', 'xr', 'gm', 'gr', 'om', 'orr')):
-        setattr(a, n_, stats[i].data_ptr())
-    nws = max(lib().genrl_sgemm_ws_floats(*s_) for s_ in _observe_shapes(B, SK, U, D))
-    ws = torch.empty(max(nws, 1), device=dev)
-    a.ws, a.ws_floats = ws.data_ptr(), nws
+    copy2d(stoch0, SK, sm, SK, B, SK)
+    copy2d(deter0, D, xh, X, B, D, dst_off=U)
     keep = _scan_fuse(a, w_s, T, B, S, K, U, dev)
     if SEQ_C and gemm_profile is None:
         check(lib().genrl_observe_seq_fwd(ctypes.byref(a), _stream()), 'observe_seq_fwd')

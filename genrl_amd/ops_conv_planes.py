@@ -19,7 +19,8 @@ from torch.autograd import Function
 from ._lib import lib, check
 from . import planes
 from . import ops
-from .ops import _p, _f32, _grad_buf, _ws, sgemm, sgemm_conv, colsum
+from .ops import _p, _f32, _ln_param_targets, sgemm, sgemm_conv
+from .streams import timed_start, timed_end
 
 _stream = ops._stream
 ENABLED = os.environ.get('GENRL_PLANES_CONV', '1') != '0'
@@ -109,15 +110,7 @@ def _ln_bwd(dy2d, pre2d, gamma, beta, mean, rstd, bias, want_planes):
     M, N = pre2d.shape
     dev = pre2d.device
     dpre = torch.empty_like(pre2d)
-    tg, tb, tc = _grad_buf(gamma), _grad_buf(beta), _grad_buf(bias)
-    direct = tg is not None and tb is not None and tc is not None
-    if direct:
-        g0, g1, g2 = tg, tb, tc
-    else:
-        gb = torch.empty(3, N, device=dev)
-        g0, g1, g2 = gb[0], gb[1], gb[2]
-    ws = _ws(lib().genrl_ln_ws_floats(M, N), dev)
-    acc_p = int(direct) | (ops.defer_reduce(M, N, ws, g0, g1, g2) if direct else 0)
+    g0, g1, g2, ws, acc_p, direct = _ln_param_targets(M, N, gamma, beta, bias, dev)
     P = None
     if want_planes and N <= 256 and N % 4 == 0 and M >= 64:
         P = planes.Planes(M, N, dev, zero=False)
@@ -136,20 +129,15 @@ def _ln_bwd(dy2d, pre2d, gamma, beta, mean, rstd, bias, want_planes):
 
 def _gemm_conv(img_p, Nimg, H, W, C, k, Bp, out, ldc, bias, N):
     """out[m, n] = sum_kk patch(m, kk) B[n, kk] (+ bias): the DMA gathers the patches from the uniform planes img_p"""
-    if planes.gemm_profile is not None:
-        e0 = torch.cuda.Event(enable_timing=True); e0.record()
+    e0 = timed_start(planes.gemm_profile)
     check(lib().genrl_gemm_h2_conv(img_p.ptr(), img_p.ld, img_p.plane, img_p.inv_ptr(), Nimg, H, W, C, k, Bp.ptr(), Bp.ld, Bp.plane,
                                    Bp.inv_ptr(), _p(out), ldc, _p(bias), N, 0, _stream()), 'gemm_h2_conv')
-    if planes.gemm_profile is not None:
-        e1 = torch.cuda.Event(enable_timing=True); e1.record()
-        Ho, Wo = (H - k) // 2 + 1, (W - k) // 2 + 1
-        planes.gemm_profile.append((Nimg * Ho * Wo, N, k * k * C, e0, e1, 'kk/conv1/h2/pipe4'))
+    timed_end(planes.gemm_profile, e0, Nimg * ((H - k) // 2 + 1) * ((W - k) // 2 + 1), N, k * k * C, 'kk/conv1/h2/pipe4')
 
 
 def _gemm_tn_conv(Ap, img_p, Nimg, H, W, C, k, out, ldc, NI, M):
     """out[i, j] = sum_m A(m, i) patch(m, j): the convolution weight gradients (A: planes with M rows; patches from img_p)"""
-    if planes.gemm_profile is not None:
-        e0 = torch.cuda.Event(enable_timing=True); e0.record()
+    e0 = timed_start(planes.gemm_profile)
     NJ = k * k * C
     nb = lib().genrl_gemm_h2_tn_ws_bytes(NI, NJ, M)
     ws = torch.empty(nb + 256, dtype=torch.uint8, device=out.device)
@@ -158,9 +146,7 @@ def _gemm_tn_conv(Ap, img_p, Nimg, H, W, C, k, out, ldc, NI, M):
     assert ro.numel() == M + 256, (ro.numel(), M)
     check(lib().genrl_gemm_h2_tn_conv(Ap.ptr(), Ap.ld, Ap.plane, Ap.inv_ptr(), img_p.ptr(), img_p.ld, img_p.plane, img_p.inv_ptr(),
                                       _p(ro), W, C, k, _p(out), ldc, NI, M, 0, wp, nb, _stream()), 'gemm_h2_tn_conv')
-    if planes.gemm_profile is not None:
-        e1 = torch.cuda.Event(enable_timing=True); e1.record()
-        planes.gemm_profile.append((NI, NJ, M, e0, e1, 'rr/conv2/h2tn/pipe4'))
+    timed_end(planes.gemm_profile, e0, NI, NJ, M, 'rr/conv2/h2tn/pipe4')
 
 
 # ---- gather ("sub-pixel") form of the scatter side: ConvTranspose2d forward / Conv2d input gradient without cols + col2im ---------
@@ -224,8 +210,7 @@ def _subpixel(xp, Nimg, Hi, Wi, Cs, Cp, k, Wsrc, s_ci, s_co, s_tap, bias, out, w
     pad = T - 1
     dev = out.device
     Hp, Wp = Hi + 2 * pad, Wi + 2 * pad
-    if planes.gemm_profile is not None:
-        e0 = torch.cuda.Event(enable_timing=True); e0.record()
+    e0 = timed_start(planes.gemm_profile)
     xq = planes.Planes(Nimg * Hp * Wp, Cs, dev, zero=False)
     assert xq.ld == xp.ld
     check(lib().genrl_pad_planes(xp.ptr(), xp.plane, xp.inv_ptr(), xq.ptr(), xq.plane, xq.inv_ptr(), Nimg, Hi, Wi, xp.ld, pad, _stream()),
@@ -247,9 +232,7 @@ def _subpixel(xp, Nimg, Hi, Wi, Cs, Cp, k, Wsrc, s_ci, s_co, s_tap, bias, out, w
     _, Ho, Wo, _ = out.shape
     check(lib().genrl_gemm_h2_subpixel(xq.ptr(), xq.ld, xq.plane, xq.inv_ptr(), Nimg, Hp, Wp, Cs, T, wp.ptr(), wp.ld, wp.plane, wp.inv_ptr(),
                                        _p(out), Ho, Wo, Cp, _p(b4), _stream()), 'gemm_h2_subpixel')
-    if planes.gemm_profile is not None:
-        e1 = torch.cuda.Event(enable_timing=True); e1.record()
-        planes.gemm_profile.append((Nimg * (Hp - T + 1) * (Wp - T + 1), 4 * Cp, K, e0, e1, 'kk/subpixel/h2/pipe4'))
+    timed_end(planes.gemm_profile, e0, Nimg * (Hp - T + 1) * (Wp - T + 1), 4 * Cp, K, 'kk/subpixel/h2/pipe4')
 
 
 def _wplanes(wsrc, Wp, transpose):
@@ -296,12 +279,9 @@ class _Conv2dS2P(Function):
             _gemm_conv(xp, Nimg, Hi, Wi, C, k, _wplanes(ctx.wsrc, Wp, False), y, Co, b, Co)
         elif u8 and _conv1_direct(x, C, k, Co, Wi):
             # the first layer straight from the frames (genrl_conv1_u8_fwd): no patch matrix, forward or backward
-            if planes.gemm_profile is not None:
-                e0 = torch.cuda.Event(enable_timing=True); e0.record()
+            e0 = timed_start(planes.gemm_profile)
             check(lib().genrl_conv1_u8_fwd(_p(x), _p(Wp), _p(b), _p(y), Nimg, Hi, Wi, Co, k, _stream()), 'conv1_u8_fwd')
-            if planes.gemm_profile is not None:
-                e1 = torch.cuda.Event(enable_timing=True); e1.record()
-                planes.gemm_profile.append((M, Co, K, e0, e1, 'kk/conv1_direct'))
+            timed_end(planes.gemm_profile, e0, M, Co, K, 'kk/conv1_direct')
             ctx.direct1 = True
         else:
             _need_fp32(x, ctx.xlazy, xp)
@@ -344,12 +324,9 @@ class _Conv2dS2P(Function):
                 _need_fp32(x, ctx.xlazy, xp)
             if getattr(ctx, 'direct1', False):
                 ws = torch.empty(lib().genrl_conv1_u8_wgrad_ws_floats(Co), device=dy.device)
-                if planes.gemm_profile is not None:
-                    e0 = torch.cuda.Event(enable_timing=True); e0.record()
+                e0 = timed_start(planes.gemm_profile)
                 check(lib().genrl_conv1_u8_wgrad(_p(x), _p(dy2), _p(dW), _p(ws), Nimg, Hi, Wi, Co, k, _stream()), 'conv1_u8_wgrad')
-                if planes.gemm_profile is not None:
-                    e1 = torch.cuda.Event(enable_timing=True); e1.record()
-                    planes.gemm_profile.append((Co, K, M, e0, e1, 'rr/conv1_direct_bwd'))
+                timed_end(planes.gemm_profile, e0, Co, K, M, 'rr/conv1_direct_bwd')
             elif tn and dyp is not None:
                 _gemm_tn_conv(dyp, xp, Nimg, Hi, Wi, C, k, dW, K, Co, M)
             elif ops._implicit_conv(x, C) and Co % 4 == 0:

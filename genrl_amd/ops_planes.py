@@ -13,7 +13,7 @@ from ._lib import lib, check
 from . import planes
 from . import planes as pl          # (module alias: `planes=` parameters below are operand handles)
 from . import ops
-from .ops import _p, _f32, _grad_buf, _ws, sgemm, colsum, UNIMIX
+from .ops import _p, _f32, _ln_param_targets, _wgrad_target, _bias_grad, sgemm, UNIMIX
 
 _stream = ops._stream
 
@@ -124,29 +124,18 @@ class ActorTapePlanes(ops.ActorTape):
             dpre = torch.empty(M, U, device=dev)
             if dpre_p is None or dpre_p.cols != U:
                 dpre_p = planes.Planes(M, U, dev)
-            tg, tbe, tc = _grad_buf(gamma), _grad_buf(beta), (_grad_buf(b) if b is not None else None)
-            direct = tg is not None and tbe is not None and (b is None or tc is not None)
-            if direct:
-                g0, g1, g2, acc_p = tg, tbe, tc, 1
-            else:
-                gb = torch.empty(3, U, device=dev)
-                g0, g1, g2, acc_p = gb[0], gb[1], gb[2], 0
-            ws = _ws(lib().genrl_ln_ws_floats(M, U), dev)
-            if direct:
-                acc_p |= ops.defer_reduce(M, U, ws, g0, g1, g2)
+            g0, g1, g2, ws, acc_p, direct = _ln_param_targets(M, U, gamma, beta, b, dev, bias_optional=True)
             _ln_bwd(_p(dy), _p(self.pre[l]), gamma, beta, _p(self.mean[l]), _p(self.rstd[l]), _p(dpre), M, U, dpre_p, 0,
                     g0, g1, g2, ws, acc_p)
-            tw = _grad_buf(W)
-            acc = tw is not None
-            dW = tw if acc else torch.empty(U, K, device=dev)
+            tw, acc, dW = _wgrad_target(W)
             # weight gradients: on the same planes through the transposing kernel (genrl_gemm_h2_tn) from TN_MIN_ROWS rows up
             tn = planes.tn_ok(M, U, K, K)
             if l > 0:
                 x = self.y[l - 1]
                 if tn:
-                    planes.gemm_tn(dpre_p, self.yp[l - 1], dW, K, U, K, M, accumulate=acc)
+                    planes.gemm_tn(dpre_p, self.yp[l - 1], tw, K, U, K, M, accumulate=acc)
                 else:
-                    sgemm(dpre, 1, U, x, 1, K, dW, K, None, U, K, M, accumulate=acc)
+                    sgemm(dpre, 1, U, x, 1, K, tw, K, None, U, K, M, accumulate=acc)
                 dy = torch.empty(M, K, device=dev)
                 planes.gemm(dpre_p, planes.weight(W, transpose=True), dy, K, None, M, K)
             else:
@@ -155,12 +144,12 @@ class ActorTapePlanes(ops.ActorTape):
                 assert x1.is_contiguous() and x2.is_contiguous() and x1.shape[0] >= H and K1 + K2 == K
                 sp_ = getattr(self, 'state_planes', None)
                 if tn and sp_ is not None and K1 % 4 == 0:
-                    planes.gemm_tn(dpre_p, sp_[0], dW, K, U, K1, M, accumulate=acc)
-                    planes.gemm_tn(dpre_p, sp_[1], dW, K, U, K2, M, accumulate=acc, c_off=K1)
+                    planes.gemm_tn(dpre_p, sp_[0], tw, K, U, K1, M, accumulate=acc)
+                    planes.gemm_tn(dpre_p, sp_[1], tw, K, U, K2, M, accumulate=acc, c_off=K1)
                 else:
-                    sgemm(dpre, 1, U, x1, 1, K1, dW, K, None, U, K1, M, accumulate=acc)
-                    sgemm(dpre, 1, U, x2, 1, K2, dW, K, None, U, K2, M, c_off=K1, accumulate=acc)
-            grads[l] = (None if acc else dW, None if (direct or b is None) else g2, None if direct else g0,
+                    sgemm(dpre, 1, U, x1, 1, K1, tw, K, None, U, K1, M, accumulate=acc)
+                    sgemm(dpre, 1, U, x2, 1, K2, tw, K, None, U, K2, M, c_off=K1, accumulate=acc)
+            grads[l] = (dW, None if (direct or b is None) else g2, None if direct else g0,
                         None if direct else g1)
         return dWh, dbh, grads
 
@@ -421,18 +410,7 @@ class _DenseLNActPlanes(Function):
         dpre = torch.empty_like(pre) if ((ctx.needs_input_grad[2] and not use_tn) or not planes_only) else None
         dpre_p = planes.Planes(M, N, dev)
         need_p = ctx.needs_input_grad[2] or ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
-        tg, tb, tc = _grad_buf(gamma), _grad_buf(beta), (_grad_buf(b) if b is not None else None)
-        direct = need_p and tg is not None and tb is not None and tc is not None
-        if direct:
-            g0, g1, g2, acc_p = tg, tb, tc, 1
-        elif need_p:
-            gb = torch.empty(3, N, device=dev)
-            g0, g1, g2, acc_p = gb[0], gb[1], gb[2], 0
-        else:
-            g0 = g1 = g2 = None; acc_p = 0
-        ws = _ws(lib().genrl_ln_ws_floats(M, N), dev) if need_p else None
-        if direct:
-            acc_p |= ops.defer_reduce(M, N, ws, g0, g1, g2)
+        g0, g1, g2, ws, acc_p, direct = _ln_param_targets(M, N, gamma, beta, b, dev, need=need_p)
         _ln_bwd(_p(dy2), _p(pre), gamma, beta, _p(mean), _p(rstd), _p(dpre) if dpre is not None else None, M, N, dpre_p, 0, g0, g1, g2, ws, acc_p)
         d1 = d2 = dW = None
         if ctx.needs_input_grad[0]:
@@ -444,10 +422,7 @@ class _DenseLNActPlanes(Function):
             planes.gemm(dpre_p, planes.weight(W, True, K1), d2, K2, None, M, K2)
             d2 = d2.reshape(ctx.shapes[1])
         if ctx.needs_input_grad[2]:
-            tgt = _grad_buf(W)
-            acc = tgt is not None
-            if not acc:
-                dW = tgt = torch.empty(N, K, device=dev)
+            tgt, acc, dW = _wgrad_target(W)
             if use_tn:
                 planes.gemm_tn(dpre_p, ip[0][0], tgt, K, N, K1, M, accumulate=acc, b_row0=ip[0][1])
                 if ctx.has2:
@@ -496,20 +471,13 @@ class _LinearPlanes(Function):
             planes.gemm(dyp, planes.weight(W, transpose=True), dx, K, None, M, K)
             dx = dx.reshape(ctx.xshape)
         if ctx.needs_input_grad[1]:
-            tgt = _grad_buf(W)
-            acc = tgt is not None
-            if not acc:
-                dW = tgt = torch.empty(N, K, device=dy.device)
+            tgt, acc, dW = _wgrad_target(W)
             if tn:
                 planes.gemm_tn(dyp, ctx.in_planes[0], tgt, K, N, K, M, accumulate=acc, b_row0=ctx.in_planes[1])
             else:
                 sgemm(dy2, 1, ldy, x2, 1, K, tgt, K, None, N, K, M, accumulate=acc)
         if b is not None and ctx.needs_input_grad[2]:
-            tgt = _grad_buf(b)
-            if tgt is not None:
-                colsum(dy2, out=tgt, accumulate=True, ld=ldy)
-            else:
-                db = colsum(dy2, ld=ldy)
+            db = _bias_grad(b, dy2, ldy)
         return dx, dW, db, None, None
 
 

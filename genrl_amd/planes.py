@@ -19,6 +19,7 @@ gemm_profile = None          # bench.py: list of (M, N, K, start_event, end_even
 
 
 from .streams import raw_current_stream as _stream      # raw hipStream_t of torch's current stream (private fast call, public fallback)
+from .streams import timed_start, timed_end
 
 
 def r64(k):
@@ -174,8 +175,7 @@ def weight(W, transpose=False, c0=0, c1=None):
 def gemm(A, B, C, ldc, bias, M, N, accumulate=False, a_row0=0, A1=None, B1=None, a1_row0=0, c_off=0, b_row0=0, b1_row0=0):
     """C[M, N] (+)= A[a_row0.., :] B^T (+ A1 B1^T) (+ bias); A, B: Planes handles; C fp32 tensor, c_off elements in"""
     assert A.ld == B.ld and a_row0 + M <= A.rows and b_row0 + N <= B.rows, (A.ld, B.ld, A.rows, B.rows, M, N)
-    if gemm_profile is not None:
-        e0 = torch.cuda.Event(enable_timing=True); e0.record()
+    e0 = timed_start(gemm_profile)
     k1 = 0
     a1 = b1 = (None, 0, 0, None)
     if A1 is not None:
@@ -185,9 +185,7 @@ def gemm(A, B, C, ldc, bias, M, N, accumulate=False, a_row0=0, A1=None, B1=None,
     check(lib().genrl_gemm_h2(A.ptr(a_row0), A.ld, A.plane, A.inv_ptr(a_row0), B.ptr(b_row0), B.ld, B.plane, B.inv_ptr(b_row0),
                               A.ld, *a1, *b1, k1, C.data_ptr() + 4 * c_off, ldc, bias.data_ptr() if bias is not None else None,
                               M, N, int(accumulate), _stream()), 'gemm_h2')
-    if gemm_profile is not None:
-        e1 = torch.cuda.Event(enable_timing=True); e1.record()
-        gemm_profile.append((M, N, A.cols + (A1.cols if A1 is not None else 0), e0, e1, 'kk/h2/pipe4'))
+    timed_end(gemm_profile, e0, M, N, A.cols + (A1.cols if A1 is not None else 0), 'kk/h2/pipe4')
 
 
 # ---- Dense -> LayerNorm (-> SiLU) in one launch (genrl_gemm_h2_ln: the column tiles of a row block exchange their row statistics inside ONE
@@ -230,8 +228,6 @@ def gemm_ln(A, B, C, bias, M, N, gamma, beta, eps, out_p, out_row0, y=None, mean
     """C[M, N] = A[a_row0.., :] B^T (+ A1 B1^T) + bias (row stride N) and, in the same launch, y = act(LayerNorm(C) gamma + beta): fp32 rows
     into `y` (row stride N, y_off elements in; None: planes only), planes into rows out_row0.. of out_p (uniform scale), mean / rstd (m_off in)"""
     assert A.ld == B.ld and a_row0 + M <= A.rows and N <= B.rows and out_p.cols == N and out_row0 + M <= out_p.rows
-    if gemm_profile is not None:
-        e0 = torch.cuda.Event(enable_timing=True); e0.record()
     k1 = 0
     a1 = b1 = (None, 0, 0, None)
     if A1 is not None:
@@ -251,6 +247,7 @@ def gemm_ln(A, B, C, bias, M, N, gamma, beta, eps, out_p, out_row0, y=None, mean
                                         rstd_.data_ptr() + 4 * (m_off if rstd is not None else 0), M, N, float(eps), int(act),
                                         out_p.ptr(out_row0), out_p.ld, out_p.plane, out_p.inv_ptr(out_row0), _stream()), 'ln_act_fwd_h2')
         return
+    e0 = timed_start(gemm_profile)       # (after the unaligned return above: that path's product is timed by gemm() itself)
     sync, part = _ln_workspace(C.device)
     check(lib().genrl_gemm_h2_ln(A.ptr(a_row0), A.ld, A.plane, A.inv_ptr(a_row0), B.ptr(0), B.ld, B.plane, B.inv_ptr(0), A.ld, *a1, *b1, k1,
                                  C.data_ptr() + 4 * c_off, N, bias.data_ptr() if bias is not None else None, M, N,
@@ -260,9 +257,7 @@ def gemm_ln(A, B, C, bias, M, N, gamma, beta, eps, out_p, out_row0, y=None, mean
                                  (rstd.data_ptr() + 4 * m_off) if rstd is not None else None,
                                  out_p.ptr(out_row0), out_p.ld, out_p.plane, out_p.inv_ptr(out_row0),
                                  (part.data_ptr() + 15) // 16 * 16, sync.data_ptr(), _stream()), 'gemm_h2_ln')
-    if gemm_profile is not None:
-        e1 = torch.cuda.Event(enable_timing=True); e1.record()
-        gemm_profile.append((M, N, A.cols + (A1.cols if A1 is not None else 0), e0, e1, 'kk/h2ln/pipe4'))
+    timed_end(gemm_profile, e0, M, N, A.cols + (A1.cols if A1 is not None else 0), 'kk/h2ln/pipe4')
 
 
 def check_ln_failure():
@@ -281,17 +276,14 @@ def gemm_sample(A, B, C, ldc, bias, M, N, q, ldq, unimix, sample, lds, SP=None, 
     """C[M, N] = A[a_row0.., :] B^T + bias AND, in the same launch, the categorical sample of every 32-class latent of the
     rows (genrl_gemm_h2_sample): one-hot rows into `sample` (fp32, s_off elements in) and their planes into SP (rows sp_row0..)"""
     assert A.ld == B.ld and a_row0 + M <= A.rows and N <= B.rows and N % 32 == 0
-    if gemm_profile is not None:
-        e0 = torch.cuda.Event(enable_timing=True); e0.record()
+    e0 = timed_start(gemm_profile)
     check(lib().genrl_gemm_h2_sample(A.ptr(a_row0), A.ld, A.plane, A.inv_ptr(a_row0), B.ptr(0), B.ld, B.plane, B.inv_ptr(0), A.ld,
                                      C.data_ptr() + 4 * c_off, ldc, bias.data_ptr() if bias is not None else None, M, N,
                                      q.data_ptr() + 4 * q_off, ldq, float(unimix), sample.data_ptr() + 4 * s_off, lds,
                                      SP.ptr(sp_row0) if SP is not None else None, SP.ld if SP is not None else 0,
                                      SP.plane if SP is not None else 0, SP.inv_ptr(sp_row0) if SP is not None else None, _stream()),
           'gemm_h2_sample')
-    if gemm_profile is not None:
-        e1 = torch.cuda.Event(enable_timing=True); e1.record()
-        gemm_profile.append((M, N, A.cols, e0, e1, 'kk/h2/pipe4'))
+    timed_end(gemm_profile, e0, M, N, A.cols, 'kk/h2/pipe4')
 
 
 def gemm_tn(A, B, C, ldc, NI, NJ, M, accumulate=False, a_row0=0, b_row0=0, c_off=0):
@@ -300,16 +292,13 @@ def gemm_tn(A, B, C, ldc, NI, NJ, M, accumulate=False, a_row0=0, b_row0=0, c_off
     into the fragments).  A, B: Planes handles with >= M rows from their first row; M % 64 == 0."""
     assert M % 64 == 0 and a_row0 + M <= A.rows and b_row0 + M <= B.rows and NI <= A.ld and NJ <= B.ld, (M, A.rows, B.rows)
     assert a_row0 % 4 == 0 and b_row0 % 4 == 0            # (the scales are read 16 bytes at a time)
-    if gemm_profile is not None:
-        e0 = torch.cuda.Event(enable_timing=True); e0.record()
+    e0 = timed_start(gemm_profile)
     nb = lib().genrl_gemm_h2_tn_ws_bytes(NI, NJ, M)
     ws = torch.empty(nb + 256, dtype=torch.uint8, device=C.device)
     wp = (ws.data_ptr() + 255) // 256 * 256
     check(lib().genrl_gemm_h2_tn(A.ptr(a_row0), A.ld, A.plane, A.inv_ptr(a_row0), B.ptr(b_row0), B.ld, B.plane, B.inv_ptr(b_row0),
                                  C.data_ptr() + 4 * c_off, ldc, NI, NJ, M, int(accumulate), wp, nb, _stream()), 'gemm_h2_tn')
-    if gemm_profile is not None:
-        e1 = torch.cuda.Event(enable_timing=True); e1.record()
-        gemm_profile.append((NI, NJ, M, e0, e1, 'rr/h2tn/pipe4'))
+    timed_end(gemm_profile, e0, NI, NJ, M, 'rr/h2tn/pipe4')
 
 
 TN_ENABLED = os.environ.get('GENRL_PLANES_WGRAD', '1') != '0'

@@ -81,3 +81,23 @@ def on_side_stream():
     cur = raw_current_stream()
     dev = torch.cuda.current_device()
     return any(k[1] == dev and s.cuda_stream == cur for k, s in _side.items())
+
+
+# ---- bench.py's GEMM event pass: HIP events around single launches.  `prof` is the calling module's `gemm_profile`, read at call time
+# (None outside that pass: one test per side and nothing else)
+
+def timed_start(prof):
+    """-> the recorded start event of the launch that follows, None when not profiling"""
+    if prof is None:
+        return None
+    e0 = torch.cuda.Event(enable_timing=True); e0.record()
+    return e0
+
+
+def timed_end(prof, e0, M, N, K, tag):
+    """close the launch opened by timed_start: append (M, N, K, start, end, tag) to `prof`.  A tag that has to be asked for after the
+    launch (the pipe the dispatcher took) is built by the caller under its own `if e0 is not None`"""
+    if e0 is None or prof is None:
+        return
+    e1 = torch.cuda.Event(enable_timing=True); e1.record()
+    prof.append((M, N, K, e0, e1, tag))
