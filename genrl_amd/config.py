@@ -120,3 +120,18 @@ def dreamer_tiny_overrides():
     r = dict(hidden=32, deter=32, stoch=4, discrete=4)
     return dict(rssm=r, reward_head=dict(units=32), actor=dict(units=32), critic=dict(units=32),
                 encoder=dict(cnn_depth=4), decoder=dict(cnn_depth=4))
+
+
+def p2e_cfg(batch_size=64, batch_length=50, device='cuda', task='walker_walk', **over):
+    """dreamer_cfg + agent/plan2explore.yaml: grad_heads [decoder], actor_ent 0, reward_norm momentum 0.95 (unused while reward_ema
+    is on, as in the reference)."""
+    base = dict(grad_heads=['decoder'], actor_ent=0, reward_norm=dict(momentum=0.95, scale=1.0, eps=1e-8))
+    base.update(over)
+    return dreamer_cfg(batch_size, batch_length, device, task, **base)
+
+
+def make_p2e_agent(cfg, act_dim=6, img=64):
+    from .agent.plan2explore import Plan2Explore
+    obs = dict(observation=Spec((3, img, img), np.uint8), is_first=Spec((), bool), is_last=Spec((), bool),
+               is_terminal=Spec((), bool))
+    return Plan2Explore(name='plan2explore', cfg=cfg, obs_space=obs, act_spec=Spec((act_dim,), np.float32))

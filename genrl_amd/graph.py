@@ -159,4 +159,6 @@ class GraphedStep:
         ag = self.agent
         ac = self._behavior(ag)
         opts = [ag.wm.model_opt, ac.actor_opt, ac.critic_opt]
+        if getattr(ag, 'disagreement_opt', None) is not None:      # Plan2Explore's ensemble
+            opts.append(ag.disagreement_opt)
         return [g for o in opts for g in o._groups]

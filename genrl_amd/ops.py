@@ -2185,3 +2185,110 @@ def rssm_imagine_seq(act, stoch0, deter0, q, S, K, W_in, b_in, g_in, be_in, W_g,
         _observe_fwd_py(a)
     del keep
     return deter, plog, pst
+
+
+# ------------------------------------------------------------------ Plan2Explore ensemble row kernels (csrc/ensemble.hip)
+
+def _plane_out(P, row0=0):
+    """(planes, ld, plane stride, inv) arguments of a row kernel's optional plane output (P: planes.Planes or None)"""
+    return (P.ptr(row0), P.ld, P.plane, P.inv_ptr(row0)) if P is not None else (None, 0, 0, None)
+
+
+def relu_fwd_raw(x, y, M, N, P=None):
+    """y = max(x, 0) over M contiguous rows of N floats (y may be x); P: planes of y"""
+    check(lib().genrl_relu_fwd_h2(_p(x), N, _p(y), N, M, N, *_plane_out(P), _stream()), 'relu_fwd_h2')
+
+
+def relu_bwd_raw(dy, y, dx, M, N, P=None):
+    """dx = dy [y > 0] (dx may be dy); P: planes of dx"""
+    check(lib().genrl_relu_bwd_h2(_p(dy), N, _p(y), N, _p(dx), N, M, N, *_plane_out(P), _stream()), 'relu_bwd_h2')
+
+
+def l2err_bwd_raw(g, err, t, p, dp, M, N, P=None):
+    """dp = -g (t - p) / err per row (0 where err = 0); P: planes of dp"""
+    check(lib().genrl_l2err_bwd(_p(g), _p(err), _p(t), N, _p(p), N, _p(dp), N, M, N, *_plane_out(P), _stream()), 'l2err_bwd')
+
+
+def ens_var_fwd_raw(preds, r, K, M, N):
+    check(lib().genrl_ens_var_fwd(_p(preds), M * N, N, K, _p(r), M, N, _stream()), 'ens_var_fwd')
+
+
+def ens_var_bwd_raw(g, preds, dp, K, M, N, P=None):
+    """dp[k] = g 2 (p_k - mean) / ((K - 1) N) (g None: 1; dp None: planes only); P: ONE Planes handle of K * M rows, member k in rows k M .."""
+    pa = (P.ptr(0), M * P.ld, P.ld, P.plane, P.inv_ptr(0), M) if P is not None else (None, 0, 0, 0, None, 0)
+    check(lib().genrl_ens_var_bwd(_p(g), _p(preds), M * N, N, K, _p(dp), M * N, N, M, N, *pa, _stream()), 'ens_var_bwd')
+
+
+class _ReLU(Function):
+    """y = max(x, 0) (nn.ReLU between a member's two Linear layers, agent/plan2explore.py:13-14); out_p: planes of y"""
+    @staticmethod
+    def forward(ctx, x, out_p):
+        x2 = _f32(x).reshape(-1, x.shape[-1]).contiguous()
+        M, N = x2.shape
+        y = torch.empty_like(x2)
+        relu_fwd_raw(x2, y, M, N, out_p)
+        ctx.save_for_backward(y)
+        return y.reshape(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        y, = ctx.saved_tensors
+        M, N = y.shape
+        dx = torch.empty_like(y)
+        relu_bwd_raw(_f32(dy).reshape(M, N).contiguous(), y, dx, M, N)
+        return dx.reshape(dy.shape), None
+
+
+def relu(x, out_planes=None):
+    return _ReLU.apply(x, out_planes)
+
+
+class _L2Err(Function):
+    """err = torch.norm(t - p, dim=-1, p=2) (agent/plan2explore.py:25-28)"""
+    @staticmethod
+    def forward(ctx, t, p):
+        t2 = _f32(t).reshape(-1, t.shape[-1]).contiguous(); p2 = _f32(p).reshape(-1, p.shape[-1]).contiguous()
+        M, N = p2.shape
+        assert t2.shape == p2.shape
+        err = torch.empty(M, device=p.device)
+        check(lib().genrl_l2err_fwd(_p(t2), N, _p(p2), N, _p(err), M, N, _stream()), 'l2err_fwd')
+        ctx.save_for_backward(t2, p2, err)
+        ctx.shape = p.shape
+        return err.reshape(p.shape[:-1])
+
+    @staticmethod
+    def backward(ctx, g):
+        t2, p2, err = ctx.saved_tensors
+        M, N = p2.shape
+        dp = torch.empty_like(p2)
+        l2err_bwd_raw(_f32(g).reshape(M).contiguous(), err, t2, p2, dp, M, N)
+        dp = dp.reshape(ctx.shape)
+        return (-dp if ctx.needs_input_grad[0] else None), (dp if ctx.needs_input_grad[1] else None)
+
+
+def l2err(t, p):
+    return _L2Err.apply(t, p)
+
+
+class _EnsVar(Function):
+    """torch.var(preds, dim=0).mean(dim=-1) of preds [K, M, E] (agent/plan2explore.py:40-41)"""
+    @staticmethod
+    def forward(ctx, preds):
+        p = _f32(preds).contiguous()
+        K, M, N = p.shape
+        r = torch.empty(M, device=p.device)
+        ens_var_fwd_raw(p, r, K, M, N)
+        ctx.save_for_backward(p)
+        return r
+
+    @staticmethod
+    def backward(ctx, g):
+        p, = ctx.saved_tensors
+        K, M, N = p.shape
+        dp = torch.empty_like(p)
+        ens_var_bwd_raw(_f32(g).contiguous(), p, dp, K, M, N)
+        return dp
+
+
+def ens_var(preds):
+    return _EnsVar.apply(preds)

@@ -6,6 +6,8 @@ the row-scaled value plus the row's inverse scale (genrl_*_h2 entry points) next
 policy weights are split once per optimiser step (planes.weight), and the products run in genrl_gemm_h2: fp32-accurate
 arithmetic on the fp16 matrix cores (three MFMAs per block and k-step) with a pure DMA + MFMA K loop.  Two-input layers ([stoch, action] -> img_in, [x, deter] -> GRU, [stoch, deter] -> policy) are ONE
 launch with two operand segments.  Weight gradients stay on the fp32-operand kernels (ops.sgemm)."""
+import os
+
 import torch
 from torch.autograd import Function
 
@@ -533,3 +535,203 @@ def imagine_rollout(stoch0, deter0, logit0, eps, q, spec):
     tape = spec.tape
     flat = [qq for l in tape.layers for qq in l[:4]]
     return _RolloutPlanes.apply(stoch0, deter0, logit0, eps, q, spec, tape.head_w, tape.head_b, *flat)
+
+
+# ---- the Plan2Explore ensemble (agent/plan2explore.py:8-41): members of Linear([obs, action]) -> ReLU -> Linear
+def _member_route(M):
+    """plane operands for the member products?  (as everywhere: from min_rows() rows up while the plane path is on -- a precision-16
+    agent has switched it off, and the fp32-operand kernels then round to bf16 themselves)"""
+    return pl.ENABLED and M >= min_rows()
+
+
+class EnsembleInputs:
+    """[obs, action] rows of an ensemble call, prepared ONCE for all members: contiguous fp32 rows and, on the plane route, their planes
+    (the action block is a second operand segment, zero padded to 64 columns: no concatenated copy)"""
+    def __init__(self, obs, action, on_planes=None):
+        self.obs = _f32(obs).reshape(-1, obs.shape[-1]).contiguous()
+        self.act = _f32(action.detach()).reshape(-1, action.shape[-1]).contiguous()
+        ops._on_gpu(self.obs, self.act)
+        self.M, self.D = self.obs.shape
+        self.A = self.act.shape[1]
+        assert self.act.shape[0] == self.M
+        self.on_planes = _member_route(self.M) if on_planes is None else on_planes
+        self.Po = pl.split(self.obs.detach()) if self.on_planes else None
+        self.Pa = pl.split(self.act) if self.on_planes else None
+
+
+def _member_fwd(inp, W0, b0, W2, b2, out=None):
+    """-> h = relu([obs, act] W0^T + b0) (M x H), its planes (plane route), out = h W2^T + b2 (M x E; into `out` if given)"""
+    M, D, A = inp.M, inp.D, inp.A
+    H, E = W0.shape[0], W2.shape[0]
+    dev = inp.obs.device
+    h = torch.empty(M, H, device=dev)
+    out = out if out is not None else torch.empty(M, E, device=dev)
+    if inp.on_planes:
+        Ph = pl.Planes(M, H, dev)
+        pl.gemm(inp.Po, pl.weight(W0, c0=0, c1=D), h, H, b0, M, H, A1=inp.Pa, B1=pl.weight(W0, c0=D))
+        ops.relu_fwd_raw(h, h, M, H, Ph)
+        pl.gemm(Ph, pl.weight(W2), out, E, b2, M, E)
+        return h, Ph, out
+    w1, ld1 = ops._aligned_block(W0, D, M)
+    sgemm(inp.obs, D, 1, w1, ld1, 1, h, H, b0, M, H, D)
+    sgemm(inp.act, A, 1, W0, D + A, 1, h, H, None, M, H, A, accumulate=True, b_off=D)
+    ops.relu_fwd_raw(h, h, M, H)
+    sgemm(h, H, 1, W2, H, 1, out, E, b2, M, E, H)
+    return h, None, out
+
+
+def _member_dgrad(inp, W0, W2, dp, dPp, p_row0, h, dobs=None, accumulate=False, c_off=0):
+    """dh = dp W2 -> ReLU backward (in `dh`, + planes on the plane route) -> optionally dobs (+)= dpre W0[:, :D].  dPp: planes of dp from row
+    p_row0 (plane route; dp may then be None).  -> dpre, its planes"""
+    M, D = inp.M, inp.D
+    H, E = W0.shape[0], W2.shape[0]
+    dev = h.device
+    dh = torch.empty(M, H, device=dev)
+    if inp.on_planes:
+        Ppre = pl.Planes(M, H, dev)
+        pl.gemm(dPp, pl.weight(W2, transpose=True), dh, H, None, M, H, a_row0=p_row0)
+        ops.relu_bwd_raw(dh, h, dh, M, H, Ppre)
+        if dobs is not None:
+            pl.gemm(Ppre, pl.weight(W0, True, 0, D), dobs, D, None, M, D, accumulate=accumulate, c_off=c_off)
+        return dh, Ppre
+    sgemm(dp, E, 1, W2, 1, H, dh, H, None, M, H, E)
+    ops.relu_bwd_raw(dh, h, dh, M, H)
+    if dobs is not None:
+        w1, ld1 = ops._aligned_block(W0, D, M)
+        sgemm(dh, H, 1, w1, 1, ld1, dobs, D, None, M, D, H, accumulate=accumulate, c_off=c_off)
+    return dh, None
+
+
+class _MemberMLP(Function):
+    """One ensemble member on [obs, action]: out = relu([obs, act] W0^T + b0) W2^T + b2, or -- with `target` -- its prediction error
+    ||target - out||_2 per row in the same node (agent/plan2explore.py:24-29), so that the error's backward hands the planes of d out
+    straight to the dgrad and weight-gradient products.  Products: plane operands (genrl_gemm_h2, weight gradients genrl_gemm_h2_tn where
+    planes.tn_ok holds) or the fp32-operand kernels, per EnsembleInputs.on_planes."""
+    @staticmethod
+    def forward(ctx, obs, W0, b0, W2, b2, inp, target):
+        h, Ph, out = _member_fwd(inp, W0, b0, W2, b2)
+        M, E = out.shape
+        ctx.inp, ctx.Ph, ctx.params = inp, Ph, (W0, b0, W2, b2)
+        if target is None:
+            ctx.save_for_backward(h)
+            ctx.err = False
+            return out.reshape(*obs.shape[:-1], E)
+        t = _f32(target.detach()).reshape(M, E).contiguous()
+        err = torch.empty(M, device=out.device)
+        check(lib().genrl_l2err_fwd(_p(t), E, _p(out), E, _p(err), M, E, _stream()), 'l2err_fwd')
+        ctx.save_for_backward(h, t, out, err)
+        ctx.err = True
+        return err
+
+    @staticmethod
+    def backward(ctx, g):
+        inp, Ph = ctx.inp, ctx.Ph
+        W0, b0, W2, b2 = ctx.params
+        M, D, A = inp.M, inp.D, inp.A
+        H, E = W0.shape[0], W2.shape[0]
+        dev = g.device
+        on_planes = inp.on_planes
+        if ctx.err:
+            h, t, out, err = ctx.saved_tensors
+            dp = torch.empty(M, E, device=dev)
+            dPp = pl.Planes(M, E, dev) if on_planes else None
+            ops.l2err_bwd_raw(_f32(g).reshape(M).contiguous(), err, t, out, dp, M, E, dPp)
+        else:
+            h, = ctx.saved_tensors
+            dp = _f32(g).reshape(M, E).contiguous()
+            dPp = pl.split(dp) if on_planes else None
+        dW0 = db0 = dW2 = db2 = dobs = None
+        if ctx.needs_input_grad[3]:
+            tgt, acc, dW2 = _wgrad_target(W2)
+            if on_planes and pl.tn_ok(M, E, H, H):
+                pl.gemm_tn(dPp, Ph, tgt, H, E, H, M, accumulate=acc)
+            else:
+                sgemm(dp, 1, E, h, 1, H, tgt, H, None, E, H, M, accumulate=acc)
+        if ctx.needs_input_grad[4]:
+            db2 = _bias_grad(b2, dp)
+        if ctx.needs_input_grad[0]:
+            dobs = torch.empty(M, D, device=dev)
+        dpre, Ppre = _member_dgrad(inp, W0, W2, dp, dPp, 0, h, dobs)
+        if ctx.needs_input_grad[1]:
+            tgt, acc, dW0 = _wgrad_target(W0)
+            K0 = D + A
+            if on_planes and pl.tn_ok(M, H, D, K0):
+                pl.gemm_tn(Ppre, inp.Po, tgt, K0, H, D, M, accumulate=acc)
+            elif on_planes and pl.tn_ok(M, H, D, D):
+                # W0's rows are D + A floats apart -- 1542 at full width: not the 16-byte rows the split-K reduce stores -- so the
+                # product lands in a compact (H, D) block and a strided copy adds it into place
+                tmp = torch.empty(H, D, device=dev)
+                pl.gemm_tn(Ppre, inp.Po, tmp, D, H, D, M)
+                ops.copy2d(tmp, D, tgt, K0, H, D, accumulate=acc)
+            else:
+                sgemm(dpre, 1, H, inp.obs, 1, D, tgt, K0, None, H, D, M, accumulate=acc)
+            sgemm(dpre, 1, H, inp.act, 1, A, tgt, K0, None, H, A, M, accumulate=acc, c_off=D)
+        if ctx.needs_input_grad[2]:
+            db0 = _bias_grad(b0, dpre)
+        return (dobs.reshape(-1, D) if dobs is not None else None), dW0, db0, dW2, db2, None, None
+
+
+def member_mlp(inp, W0, b0, W2, b2, target=None):
+    """inp: EnsembleInputs.  -> prediction (M x E), or with `target` the row-wise L2 prediction error (M)"""
+    return _MemberMLP.apply(inp.obs, W0, b0, W2, b2, inp, target)
+
+
+def disagreement_chunk_rows():
+    """rows of get_disagreement processed at a time (GENRL_P2E_CHUNK overrides): bounds its workspace, see _Disagreement"""
+    return int(os.environ.get('GENRL_P2E_CHUNK', 4096))
+
+
+class _Disagreement(Function):
+    """r[m] = mean_e var_k member_k([obs, act])[m, e] (agent/plan2explore.py:33-41) for FROZEN members, in row chunks.
+
+    r[m] depends on row m of obs alone, so d loss / d obs[m] = g[m] J[m] with J[m] = d r[m] / d obs[m]: the forward computes r AND J chunk by
+    chunk (members' forward, variance, its backward with g = 1 emitting the planes of every d pred_k, the two dgrad products per member) and
+    drops every activation at the chunk's end; the backward is one row scaling.  Nothing of size rows x 6144 outlives a chunk: at most
+    (3 K + 2) blocks of C x max(E, H) floats are live for C chunk rows whatever the row count (K predictions, K hidden activations, the
+    planes of K d pred, one d hidden + planes: 1.7 GB at K = 5, C = 4096, 6144 wide), plus J (rows x obs width).  The members' weights get no gradient here: the reference evaluates the reward with the ensemble frozen."""
+    @staticmethod
+    def forward(ctx, obs, act, K, *params):
+        if any(ctx.needs_input_grad[3:]):
+            raise ops.GenrlHipError('get_disagreement differentiates through frozen members only (train them through Disagreement.forward)')
+        obs2 = _f32(obs).reshape(-1, obs.shape[-1]).contiguous()
+        act2 = _f32(act).reshape(-1, act.shape[-1]).contiguous()
+        M, D = obs2.shape
+        dev = obs2.device
+        need_j = ctx.needs_input_grad[0]
+        r = torch.empty(M, device=dev)
+        J = torch.empty(M, D, device=dev) if need_j else None
+        on_planes = _member_route(M)
+        C = disagreement_chunk_rows()
+        E = params[2].shape[0]
+        for c0 in range(0, M, C):
+            c1 = min(M, c0 + C)
+            n = c1 - c0
+            inp = EnsembleInputs(obs2[c0:c1], act2[c0:c1], on_planes)
+            preds = torch.empty(K, n, E, device=dev)
+            hs = []
+            for k in range(K):
+                hs.append(_member_fwd(inp, *params[4 * k:4 * k + 4], out=preds[k])[0])
+            ops.ens_var_fwd_raw(preds, r[c0:c1], K, n, E)
+            if not need_j:
+                continue
+            dPp = pl.Planes(K * n, E, dev) if on_planes else None
+            dp = None if on_planes else torch.empty(K, n, E, device=dev)
+            ops.ens_var_bwd_raw(None, preds, dp, K, n, E, dPp)
+            for k in range(K):
+                W0, _, W2, _ = params[4 * k:4 * k + 4]
+                _member_dgrad(inp, W0, W2, dp[k] if dp is not None else None, dPp, k * n, hs[k], J, accumulate=k > 0, c_off=c0 * D)
+        if need_j:
+            ctx.save_for_backward(J)          # (saved, not an attribute: a retained graph may run this backward again)
+        ctx.oshape = obs.shape
+        return r
+
+    @staticmethod
+    def backward(ctx, g):
+        J, = ctx.saved_tensors
+        return (J * g.reshape(-1, 1)).reshape(ctx.oshape), None, None, *([None] * (len(ctx.needs_input_grad) - 3))
+
+
+def get_disagreement(obs, action, members):
+    """members: [(W0, b0, W2, b2), ...] -> (rows,) disagreement; differentiable w.r.t. obs"""
+    flat = [q for m in members for q in m]
+    return _Disagreement.apply(obs, action.detach(), len(members), *flat)

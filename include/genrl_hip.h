@@ -599,6 +599,26 @@ int genrl_adam_step(float* p, float* g, float* m, float* v, long n, const float*
                     void* stream);
 int genrl_scale(float* p, long n, float s, void* stream);
 
+/* ---- Plan2Explore ensemble (agent/plan2explore.py:8-41; genrl_amd/csrc/ensemble.hip): the row kernels around a member's two products.
+ * Rows of N floats, N % 4 == 0 (tested to 12 288), any row pitch that is a multiple of 4 floats, 16-byte aligned bases; returns 1 otherwise.
+ * Plane outputs (yp / dxp / dpp; NULL: none) follow the contract of genrl_ln_act_fwd_h2: planes [.][ldp] `plane` elements apart, inv[row],
+ * the row maximum taken over the kernel's output row, columns beyond N untouched -- bit-identical to genrl_split_h2 of the fp32 output.
+ * genrl_relu_fwd_h2: y = max(x, 0) (y may be x).  genrl_relu_bwd_h2: dx = dy [y > 0] (dx may be dy).
+ * genrl_l2err_fwd: err[m] = || t[m, :] - p[m, :] ||_2.  genrl_l2err_bwd: dp[m, :] = -g[m] (t - p) / err[m]; a row with err = 0 gets zeros.
+ * genrl_ens_var_fwd: K member predictions p[k] = p + k * member (2 <= K <= 8), r[m] = mean_e of the unbiased variance over k (two passes per
+ * element over the K values in registers).  genrl_ens_var_bwd: dp[k][m][e] = g[m] 2 (p_k - mean_k) / ((K - 1) N) (g NULL: 1) into dp + k * dmember
+ * (dp NULL with dpp given: planes only) and, with dpp, the planes of every dp_k: member k at dpp + k * pmember, inv + k * imember. */
+int genrl_relu_fwd_h2(const float* x, long ldx, float* y, long ldy, int M, int N, uint16_t* yp, long ldp, long plane, float* inv,
+                      void* stream);
+int genrl_relu_bwd_h2(const float* dy, long lddy, const float* y, long ldy, float* dx, long lddx, int M, int N, uint16_t* dxp, long ldp,
+                      long plane, float* inv, void* stream);
+int genrl_l2err_fwd(const float* t, long ldt, const float* p, long ldp, float* err, int M, int N, void* stream);
+int genrl_l2err_bwd(const float* g, const float* err, const float* t, long ldt, const float* p, long ldp, float* dp, long lddp, int M,
+                    int N, uint16_t* dpp, long ldpl, long plane, float* inv, void* stream);
+int genrl_ens_var_fwd(const float* p, long member, long ld, int K, float* r, int M, int N, void* stream);
+int genrl_ens_var_bwd(const float* g, const float* p, long member, long ld, int K, float* dp, long dmember, long lddp, int M, int N,
+                      uint16_t* dpp, long pmember, long ldpl, long plane, float* inv, long imember, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
