@@ -330,13 +330,25 @@ class WorldModel(Module):  # ref :120-321
         rssm = self.rssm
         seq = {k: [v] for k, v in start.items()}
         seq['action'] = [torch.zeros(N, A, device=dev)]
-        # the two heads of DistLayer('normal') (mean, std) as ONE product: weights stacked once per rollout
+        # the policy's head by its distribution: DistLayer 'normal' (dreamer_v3 / genrl defaults) or 'trunc_normal' (dreamer_v2)
+        trunc = policy._out._dist == 'trunc_normal'
+        if trunc:
+            head_mean = lambda raw: ops.trunc_normal_mean_std(raw, policy._out._min_std, policy._out._init_std)[0]
+            head_sample = lambda raw, e: ops.trunc_normal_sample(raw, e, policy._out._min_std, policy._out._init_std)
+        else:
+            assert policy._out._dist == 'normal', policy._out._dist
+            head_mean = lambda raw: ops.actor_mean_std(raw, policy._out._min_std, policy._out._max_std)[0]
+            head_sample = lambda raw, e: ops.actor_sample(raw, e, policy._out._min_std, policy._out._max_std)
+        # the two heads of DistLayer('normal' / 'trunc_normal') (mean, std) as ONE product: weights stacked once per rollout
         head_w = torch.cat([policy._out._out.weight, policy._out._std.weight], 0)
         head_b = torch.cat([policy._out._out.bias, policy._out._std.bias], 0)
         raws = []
         # training rollouts: the policy's H backward passes are batched into one over all H*N rows
+        # (the tape, the fused rollout and their C launch loops have the LayerNorm launches and the Normal head built in: a norm-free
+        # world model or policy, or a truncated-normal head, takes the step-by-step loop below)
         tape = None
-        if torch.is_grad_enabled() and head_w.requires_grad and horizon > 1 and policy._norm != 'none':
+        if (torch.is_grad_enabled() and head_w.requires_grad and horizon > 1 and policy._norm != 'none' and rssm._norm != 'none'
+                and not trunc):
             layers = [(getattr(policy, f'dense{i}').weight, getattr(policy, f'dense{i}').bias,
                        getattr(policy, f'norm{i}')._layer.weight, getattr(policy, f'norm{i}')._layer.bias,
                        getattr(policy, f'norm{i}')._layer.eps) for i in range(policy._layers)]
@@ -369,10 +381,7 @@ class WorldModel(Module):  # ref :120-321
                 else:
                     raw = ops.linear(policy.trunk(stop_gradient(s_flat), stop_gradient(deter)), head_w, head_b)
                 raws.append(raw)
-                if eval_policy:
-                    action = ops.actor_mean_std(raw, policy._out._min_std, policy._out._max_std)[0]
-                else:
-                    action = ops.actor_sample(raw, eps[h], policy._out._min_std, policy._out._max_std)
+                action = head_mean(raw) if eval_policy else head_sample(raw, eps[h])
                 x = common._dense_ln_silu(s_flat, rssm._img_in[0], rssm._img_in[1], action)
                 deter = ops.gru_step(x, deter, rssm._cell._layer.weight, rssm._cell._norm.weight, rssm._cell._norm.bias)
                 logit = rssm._prior_logits(deter)
@@ -430,14 +439,17 @@ class ActorCritic(Module):  # ref :323-462
         assert self.actor_grad == 'dynamics', 'GenRL trains the actor through the dynamics'
         self.actor = common.MLP(feat_size, act_spec.shape[0], **self.cfg.actor)
         self.critic = common.MLP(feat_size, (1,), **self.cfg.critic)
-        assert self.cfg.slow_target and self.cfg.reward_ema
+        assert self.cfg.slow_target
         self._target_critic = common.MLP(feat_size, (1,), **self.cfg.critic)
         self._updates = 0
         self.actor_opt = common.Optimizer('actor', self.actor.parameters(), **self.cfg.actor_opt, use_amp=self._use_amp)
         self.critic_opt = common.Optimizer('critic', self.critic.parameters(), **self.cfg.critic_opt, use_amp=self._use_amp)
-        self.register_buffer('ema_vals', torch.zeros((2,)).to(self.device))
-        self.reward_ema = common.RewardEMA(device=self.device)
-        self.rewnorm = common.StreamNorm(momentum=1, scale=1.0, device=self.device)
+        if self.cfg.reward_ema:         # ref :348-354
+            self.register_buffer('ema_vals', torch.zeros((2,)).to(self.device))
+            self.reward_ema = common.RewardEMA(device=self.device)
+            self.rewnorm = common.StreamNorm(momentum=1, scale=1.0, device=self.device)
+        else:
+            self.rewnorm = common.StreamNorm(**self.cfg.reward_norm, device=self.device)
         with torch.no_grad():
             for p in self.critic._out.parameters():
                 p.data = p.data * 0
@@ -464,11 +476,13 @@ class ActorCritic(Module):  # ref :323-462
             seq['reward'], mets1 = self.rewnorm(reward)
             mets1 = {f'reward_{k}': v for k, v in mets1.items()}
             target, mets2, baseline = self.target(seq)
+            self._critic_target = None
             actor_loss, mets3 = self.actor_loss(seq, target, baseline)
             seq_d = _ImaginedSeq(getattr(seq, '_rssm', None), {k: stop_gradient(v) for k, v in seq.items()})
             seq_d.unit_weight = getattr(seq, 'unit_weight', False)
             seq_d.planes = getattr(seq, 'planes', None)
-            target_d = stop_gradient(target)
+            target_d = stop_gradient(target) if self._critic_target is None else self._critic_target
+            self._critic_target = None
 
             def critic_step():
                 with common.RequiresGrad(self.critic):
@@ -495,11 +509,15 @@ class ActorCritic(Module):  # ref :323-462
 
     def actor_loss(self, seq, target, baseline):  # ref :392-429 (actor_grad 'dynamics')
         metrics = {}
-        offset, scale = self.reward_ema(target, self.ema_vals)
         ent_scale = self.cfg.actor_ent
         weight = stop_gradient(seq['weight'])
-        fused = ent_scale == 0 and getattr(self.reward_ema, 'last', None) is not None
-        if fused:
+        ema = bool(self.cfg.reward_ema)
+        if ema:
+            offset, scale = self.reward_ema(target, self.ema_vals)
+        fused = ema and ent_scale == 0 and getattr(self.reward_ema, 'last', None) is not None
+        if not ema:                     # ref :409-411: the raw lambda-return, no 'normed_target_*' / 'reward_ema_*' metrics
+            objective = target[1:]
+        elif fused:
             # normalisation, weighted mean, sign and the two 'normed_target' statistics: one launch forward, one backward
             actor_loss, st = ops.actor_objective(target, None if getattr(seq, 'unit_weight', False) else weight[:-2],
                                                  self.reward_ema.last)
@@ -522,15 +540,29 @@ class ActorCritic(Module):  # ref :323-462
         raw = raw[:n_pol]
         A = raw.shape[-1] // 2
         mn, mx = self.actor._out._min_std, self.actor._out._max_std
-        if ent_scale != 0:
-            std = (mx - mn) * torch.sigmoid(raw[..., A:] + 2.0) + mn
-            ent = (0.5 + 0.5 * np.log(2 * np.pi) + torch.log(std)).sum(-1)[:, :, None]
-            objective = objective + ent_scale * ent
+        trunc = self.actor._out._dist == 'trunc_normal'
+        if ent_scale != 0 or trunc:
+            # (the entropy of the untruncated Normal in both cases; with a truncated-normal head and scale 0 it is a metric only)
+            with contextlib.nullcontext() if ent_scale != 0 else torch.no_grad():
+                if trunc:           # ref dreamer_utils.py:832
+                    std = 2.0 * torch.sigmoid((raw[..., A:] + self.actor._out._init_std) / 2.0) + mn
+                else:
+                    std = (mx - mn) * torch.sigmoid(raw[..., A:] + 2.0) + mn
+                ent = (0.5 + 0.5 * np.log(2 * np.pi) + torch.log(std)).sum(-1)[:, :, None]
+            if ent_scale != 0:
+                objective = objective + ent_scale * ent
+                if not ema:
+                    # the reference's `objective += ent_scale * ent` (ref :423) works IN PLACE on `normed_target[1:]`, which without the
+                    # return EMA is a view of the lambda-returns themselves (ref :410, :414): the critic that follows regresses onto
+                    # returns that carry the entropy bonus from step 1 on.  Restated, not imitated: the returns stay untouched here
+                    self._critic_target = torch.cat([target[:1], objective], 0).detach()
             metrics['actor_ent'] = ent.detach().mean()
         else:                           # a metric only: no backward through it (its scale is 0); one launch
             metrics['actor_ent'] = ops.normal_entropy_mean(raw, mn, mx)
         metrics['actor_ent_scale'] = ent_scale
-        if not fused:
+        if not ema:                     # -(weight[:-2] * objective).mean() as one node
+            actor_loss = ops.wmean(objective, None if getattr(seq, 'unit_weight', False) else weight[:-2], -1.0)
+        elif not fused:
             actor_loss = -(weight[:-2] * objective).mean()
         return actor_loss, metrics
 

@@ -6,8 +6,8 @@ pickled agents are interchangeable; every forward/backward runs in the hand-writ
 of libgenrl_hip.so (genrl_amd/ops.py).  nn.Module containers (nn.Linear, nn.Conv2d, nn.LayerNorm)
 are used only as *parameter holders*: their torch forward is never called on the hot path.
 
-Only what the GenRL path configures is implemented (norm 'layer'/'none', act SiLU, discrete
-latents, GRU cell, dists mse / twohot / normal / onehot); other reference options raise.
+What the GenRL path and the dreamer_v3 / dreamer_v2 defaults configure is implemented (norm 'layer'/'none', act SiLU, discrete
+latents, GRU cell, dists mse / twohot / normal / trunc_normal / onehot, image_dist mse / normal_unit_std); other reference options raise.
 """
 import contextlib
 import re
@@ -59,6 +59,34 @@ class MSEDist:
         like = ops.mse_like(self._mode.reshape((-1,) + tuple(self._mode.shape[-3:])),
                             value.reshape((-1,) + tuple(value.shape[-3:])))
         return like.reshape(lead)
+
+
+class NormalUnitStdDist(MSEDist):
+    """Independent(Normal(mode, 1.0), 3) of the decoder with `image_dist: normal_unit_std` (ref :704): per frame
+    log_prob = -1/2 sum (mode - x)^2 - 1/2 D log 2 pi = MSEDist's log_prob (the same kernel) halved, minus a constant."""
+    def log_prob(self, value):
+        D = int(np.prod(self._mode.shape[-3:]))
+        return super().log_prob(value) * 0.5 - 0.5 * D * float(np.log(2.0 * np.pi))
+
+
+class MSEHeadDist:
+    """MSEDist on an MLP head (ref :62-83 through DistLayer 'mse', :808-809; the one-wide reward / critic heads of
+    conf/defaults/dreamer_v2.yaml): log_prob(x) = -(out - x)^2 summed over the event dimension, mean = out."""
+    def __init__(self, mode):
+        self._mode = mode
+
+    @property
+    def mean(self):
+        return self._mode
+
+    def mode(self):
+        return self._mode
+
+    def log_prob(self, value):
+        assert self._mode.shape == value.shape, (self._mode.shape, value.shape)
+        if self._mode.shape[-1] == 1:
+            return ops.sqerr_like(self._mode, value)
+        raise NotImplementedError('mse heads wider than one output are not configured by any shipped defaults')
 
 
 class TwoHotDist:
@@ -131,6 +159,29 @@ class NormalDist:
 
     def entropy(self):
         std = ops.actor_mean_std(self.raw, self.min_std, self.max_std)[1]
+        return (0.5 + 0.5 * np.log(2 * np.pi) + torch.log(std)).sum(-1)
+
+
+class TruncNormalDist:
+    """Independent(TruncatedNormal(tanh(out), std), 1) of DistLayer 'trunc_normal' (ref :830-834, tools/utils.py:102-123):
+    std = 2 sigmoid((raw_std + init_std) / 2) + min_std; a sample is clamped to [-1 + 1e-6, 1 - 1e-6] in value with the identity as
+    its gradient; mean and entropy are the untruncated Normal's (pyd.Normal's, which the reference inherits)."""
+    def __init__(self, raw, min_std, init_std, site='actor'):
+        self.raw, self.min_std, self.init_std, self.site = raw, min_std, init_std, site
+
+    def sample(self):
+        A = self.raw.shape[-1] // 2
+        eps = noise.draw('normal', self.site, tuple(self.raw.shape[:-1]) + (A,), self.raw.device)
+        return ops.trunc_normal_sample(self.raw, eps, self.min_std, self.init_std)
+
+    rsample = sample
+
+    @property
+    def mean(self):
+        return ops.trunc_normal_mean_std(self.raw, self.min_std, self.init_std)[0]
+
+    def entropy(self):
+        std = ops.trunc_normal_mean_std(self.raw, self.min_std, self.init_std)[1]
         return (0.5 + 0.5 * np.log(2 * np.pi) + torch.log(std)).sum(-1)
 
 
@@ -222,19 +273,20 @@ class ImgChLayerNorm(nn.Module):  # ref :1031-1040 (parameter holder; applied on
 
 def _dense_ln_silu(x, lin, norm, x2=None, planes=None):
     """Linear (+ second concatenated input) + LayerNorm + SiLU with the reference's layer objects.  planes: h2 planes of
-    the inputs (genrl_amd/planes.py) when the caller has them."""
-    if norm._layer is None:
-        return ops_silu(None)
+    the inputs (genrl_amd/planes.py) when the caller has them.  NormLayer('none') (conf/defaults/dreamer_v2.yaml): Linear without
+    bias + SiLU (dense_act), under the same row threshold and switch."""
     rows = x.numel() // x.shape[-1]
+    if norm._layer is None:
+        assert lin.bias is None, 'a norm-free layer has no bias (ref :339-346, :734)'
+        if (pl.ENABLED and x.is_cuda and rows >= ops_planes.min_rows() and lin.weight.shape[0] % 4 == 0
+                and os.environ.get('GENRL_PLANES_MLP', '1') != '0'):
+            return ops_planes.dense_act(x, x2, lin.weight, planes=planes)
+        return ops.dense_act(x, x2, lin.weight)
     if (pl.ENABLED and x.is_cuda and rows >= ops_planes.min_rows() and lin.weight.shape[0] % 4 == 0
             and os.environ.get('GENRL_PLANES_MLP', '1') != '0'):  # (-0.75 ms/step at c2 with the BK-64 128x128 tile, DESIGN 4a)
         return ops_planes.dense_ln_act(x, x2, lin.weight, lin.bias, norm._layer.weight, norm._layer.bias, norm._layer.eps,
                                    planes=planes)
     return ops.dense_ln_act(x, x2, lin.weight, lin.bias, norm._layer.weight, norm._layer.bias, norm._layer.eps)
-
-
-def ops_silu(x):
-    raise NotImplementedError('norm: none is not on the GenRL path (conf/defaults/genrl.yaml uses layer)')
 
 
 class GRUCell(Module):  # ref :750-785
@@ -266,7 +318,7 @@ class DistLayer(Module):  # ref :787-841
         self._shape = shape if type(shape) in [list, tuple] else [shape]
         self._dist, self._min_std, self._init_std, self._max_std = dist, min_std, init_std, max_std
         self._out = nn.Linear(in_dim, int(np.prod(shape)), bias=bias)
-        if dist == 'normal':
+        if dist in ('normal', 'trunc_normal'):
             self._std = nn.Linear(in_dim, int(np.prod(shape)))
         elif dist not in ('twohot', 'mse', 'onehot'):
             raise NotImplementedError(dist)
@@ -274,11 +326,11 @@ class DistLayer(Module):  # ref :787-841
     def raw(self, inputs):
         h = getattr(inputs, '_planes', None)          # the trunk's last layer left its output's operand planes (ops_planes)
         rows = inputs.numel() // inputs.shape[-1]
-        if (h is not None and pl.ENABLED and self._dist != 'normal' and rows >= ops_planes.min_rows()
+        if (h is not None and pl.ENABLED and self._dist not in ('normal', 'trunc_normal', 'mse') and rows >= ops_planes.min_rows()
                 and os.environ.get('GENRL_PLANES_LINEAR', '1') != '0'):
             return ops_planes.linear(inputs, self._out.weight, self._out.bias, h)
         out = ops.linear(inputs, self._out.weight, self._out.bias)
-        if self._dist == 'normal':
+        if self._dist in ('normal', 'trunc_normal'):
             std = ops.linear(inputs, self._std.weight, self._std.bias)
             return torch.cat([out, std], -1)
         return out
@@ -287,10 +339,12 @@ class DistLayer(Module):  # ref :787-841
         raw = self.raw(inputs)
         if self._dist == 'normal':
             return NormalDist(raw, self._min_std, self._max_std)
+        if self._dist == 'trunc_normal':
+            return TruncNormalDist(raw, self._min_std, self._init_std)
         if self._dist == 'twohot':
             return TwoHotDist(raw)
         if self._dist == 'mse':
-            return MSEDist(raw.reshape(list(inputs.shape[:-1]) + list(self._shape)))
+            return MSEHeadDist(raw.reshape(list(inputs.shape[:-1]) + list(self._shape)))
         if self._dist == 'onehot':
             return OneHotDist(raw)
         raise NotImplementedError(self._dist)
@@ -390,7 +444,8 @@ class Decoder(Module):  # ref :631-715
         self._embed_dim, self._shapes = embed_dim, shapes
         self.cnn_keys = [k for k, v in shapes.items() if re.match(cnn_keys, k) and len(v) == 3]
         self.mlp_keys = [k for k, v in shapes.items() if re.match(mlp_keys, k) and len(v) == 1]
-        assert act == 'SiLU' and norm == 'layer' and image_dist == 'mse'
+        assert act == 'SiLU' and norm == 'layer' and image_dist in ('mse', 'normal_unit_std')
+        self._image_dist = image_dist
         assert len(self.mlp_keys) == 0 and len(self.cnn_keys) == 1
         self._cnn_depth, self._cnn_kernels = cnn_depth, cnn_kernels
         self.channels = {k: self._shapes[k][0] for k in self.cnn_keys}
@@ -427,7 +482,8 @@ class Decoder(Module):  # ref :631-715
                 x = convT2d(x, conv.weight, conv.bias, ln=(ln.norm.weight, ln.norm.bias, ln.norm.eps), fp32_out=nxt, planes_out=i != n - 2)
             else:
                 x = ops.convT2d_s2(x, conv.weight, conv.bias, out_nchw=True)     # frames leave in the reference's NCHW
-        return {key: MSEDist(x.reshape(tuple(lead) + tuple(x.shape[1:]))) for key in self.channels}
+        image_dist = NormalUnitStdDist if self._image_dist == 'normal_unit_std' else MSEDist          # ref :704
+        return {key: image_dist(x.reshape(tuple(lead) + tuple(x.shape[1:]))) for key in self.channels}
 
 
 # ----------------------------------------------------------------------------- RSSM
@@ -448,8 +504,8 @@ class EnsembleRSSM(Module):  # ref :302-555
                  single_obs_posterior=False, cell_input='stoch', cell_type='gru'):
         super().__init__()
         assert action_dim is not None
-        assert discrete and ensemble == 1 and cell_type == 'gru' and cell_input == 'stoch' and norm == 'layer', \
-            'GenRL path: discrete latents, ensemble 1, GRU, layer norm'
+        assert discrete and ensemble == 1 and cell_type == 'gru' and cell_input == 'stoch' and norm in ('layer', 'none'), \
+            'discrete latents, ensemble 1, GRU, norm layer / none'
         self.device = device
         self._embed_dim, self._action_dim, self._ensemble = embed_dim, action_dim, ensemble
         self._stoch, self._deter, self._hidden, self._discrete = stoch, deter, hidden, discrete
@@ -458,11 +514,12 @@ class EnsembleRSSM(Module):  # ref :302-555
         self._cell = GRUCell(self._hidden, self._deter, norm=True, device=self.device)
         self._ensemble_img_dist = nn.ModuleList([nn.Linear(hidden, stoch * discrete) for _ in range(ensemble)])
         self._obs_dist = nn.Linear(hidden, stoch * discrete)
-        self._img_in = nn.Sequential(nn.Linear(stoch * discrete + action_dim, hidden), NormLayer(norm, hidden))
+        bias = norm != 'none'              # (a norm-free layer has no bias, ref :339-346; the GRU cell keeps its LayerNorm, ref :322)
+        self._img_in = nn.Sequential(nn.Linear(stoch * discrete + action_dim, hidden, bias=bias), NormLayer(norm, hidden))
         self._ensemble_img_out = nn.ModuleList(
-            [nn.Sequential(nn.Linear(deter, hidden), NormLayer(norm, hidden)) for _ in range(ensemble)])
+            [nn.Sequential(nn.Linear(deter, hidden, bias=bias), NormLayer(norm, hidden)) for _ in range(ensemble)])
         in_obs = embed_dim if single_obs_posterior else deter + embed_dim
-        self._obs_out = nn.Sequential(nn.Linear(in_obs, hidden), NormLayer(norm, hidden))
+        self._obs_out = nn.Sequential(nn.Linear(in_obs, hidden, bias=bias), NormLayer(norm, hidden))
 
     # ---- shapes / helpers
     def initial(self, batch_size):
@@ -542,7 +599,8 @@ class EnsembleRSSM(Module):  # ref :302-555
         sequential (ops.gru_seq).  Without it, falls back to the step-by-step form."""
         B, T = action.shape[:2]
         if not self.single_obs_posterior:
-            if os.environ.get('GENRL_OBSERVE_SEQ', '1') == '0':
+            # (the scan's C launch loop has the LayerNorm launches of `norm: layer` built in: norm-free layers go step by step)
+            if self._norm == 'none' or os.environ.get('GENRL_OBSERVE_SEQ', '1') == '0':
                 return self._observe_stepwise(embed, action, is_first, state)
             return self._observe_scan(embed, action, is_first, state)
         S, K = self._stoch, self._discrete
@@ -614,7 +672,8 @@ class EnsembleRSSM(Module):  # ref :302-555
         """ref :373-381: prior rollout for given actions (B,T,A)."""
         B, T = action.shape[:2]
         state = state if state is not None else self.initial(B)
-        if not torch.is_grad_enabled() and action.is_cuda and os.environ.get('GENRL_OBSERVE_SEQ', '1') != '0':
+        if (not torch.is_grad_enabled() and action.is_cuda and self._norm != 'none'
+                and os.environ.get('GENRL_OBSERVE_SEQ', '1') != '0'):
             # forward only (the data-free block's warm-up rollouts, report, video_imagine all run under no_grad): the action half of
             # `_img_in` batched over T, the eight launches per step of the remaining chain from ONE host call (csrc/seq.hip)
             S, K = self._stoch, self._discrete

@@ -1,7 +1,7 @@
 """MI355X-native `agent/plan2explore.py`: Disagreement and Plan2Explore with the reference's API (mazpie/genrl
 agent/plan2explore.py) on top of the HIP kernels.  Same constructor signatures, attribute / method / metric names and
 state_dict keys (`disagreement.ensemble.{k}.{0,2}.{weight,bias}`); the ensemble's products and row kernels are
-genrl_amd/ops_planes.py's member_mlp / get_disagreement (csrc/ensemble.hip).  Supported on the dreamer_v3 defaults."""
+genrl_amd/ops_planes.py's member_mlp / get_disagreement (csrc/ensemble.hip).  Supported on the dreamer_v3 and dreamer_v2 defaults."""
 import torch
 import torch.nn as nn
 

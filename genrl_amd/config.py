@@ -88,9 +88,31 @@ def tiny_overrides():
                 encoder=dict(cnn_depth=4), decoder=dict(cnn_depth=4))
 
 
-def dreamer_cfg(batch_size=64, batch_length=50, device='cuda', task='walker_walk', **over):
-    """conf/defaults/dreamer_v3.yaml + conf/env/dmc_pixels.yaml + agent/dreamer.yaml (BASELINE
-    configs[2]: DreamerAgent, walker A=6)."""
+def dreamer_v2_settings():
+    """What conf/defaults/dreamer_v2.yaml sets differently from dreamer_v3.yaml (config data, restated): norm-free RSSM / MLP layers,
+    one-wide mse heads for reward and critic, a truncated-normal actor, a unit-variance image likelihood, KL balance 0.8 at scale 1, no
+    return EMA (the reward goes through StreamNorm(**reward_norm) instead) and the v2 optimiser values.  `act: elu` is a comment in that
+    file: the activation stays SiLU.  `precision: 16` there is forced to 32 like everywhere in this module."""
+    return dict(
+        rssm=dict(ensemble=1, hidden=512, deter=512, stoch=32, discrete=32, norm='none', std_act='softplus', min_std=0.1,
+                  single_obs_posterior=False),
+        reward_head=dict(layers=4, units=512, norm='none', dist='mse'),
+        kl=dict(free=1.0, forward=False, balance=0.8, free_avg=False),
+        loss_scales=dict(kl=1.0, reward=1.0, discount=1.0, proprio=1.0),
+        model_opt=dict(opt='adam', lr=3e-4, eps=1e-5, clip=1000, wd=1e-6),
+        decoder_inputs='feat', image_dist='normal_unit_std',
+        actor=dict(layers=4, units=512, norm='none', dist='trunc_normal', min_std=0.1),
+        critic=dict(layers=4, units=512, norm='none', dist='mse'),
+        actor_opt=dict(opt='adam', lr=8e-5, eps=1e-5, clip=100, wd=1e-6),
+        critic_opt=dict(opt='adam', lr=8e-5, eps=1e-5, clip=100, wd=1e-6),
+        discount=0.99, discount_lambda=0.95, slow_target=True, slow_target_update=100, slow_target_fraction=1,
+        slow_baseline=True, reward_ema=False, imag_horizon=15, precision=32)
+
+
+def dreamer_cfg(batch_size=64, batch_length=50, device='cuda', task='walker_walk', defaults='dreamer_v3', **over):
+    """conf/defaults/dreamer_v3.yaml (defaults='dreamer_v2': dreamer_v2.yaml, see dreamer_v2_settings) + conf/env/dmc_pixels.yaml +
+    agent/dreamer.yaml (BASELINE configs[2]: DreamerAgent, walker A=6)."""
+    assert defaults in ('dreamer_v3', 'dreamer_v2'), defaults
     rssm = dict(ensemble=1, hidden=512, deter=512, stoch=32, discrete=32, norm='layer', std_act='softplus', min_std=0.1,
                 single_obs_posterior=False)
     cfg = default_cfg(batch_size, batch_length, device, task)
@@ -101,6 +123,8 @@ def dreamer_cfg(batch_size=64, batch_length=50, device='cuda', task='walker_walk
                         decoder_inputs='feat', actor=dict(layers=4, units=512, norm='layer', dist='normal', min_std=0.1),
                         critic=dict(layers=4, units=512, norm='layer', dist='twohot'), imag_horizon=15,
                         grad_heads=['decoder', 'reward'], actor_ent=3e-4)))
+    if defaults == 'dreamer_v2':
+        cfg.update(_ad(dreamer_v2_settings()))
     for k, v in over.items():
         if isinstance(v, dict) and isinstance(cfg.get(k), dict):
             cfg[k].update(v)
@@ -124,7 +148,7 @@ def dreamer_tiny_overrides():
 
 def p2e_cfg(batch_size=64, batch_length=50, device='cuda', task='walker_walk', **over):
     """dreamer_cfg + agent/plan2explore.yaml: grad_heads [decoder], actor_ent 0, reward_norm momentum 0.95 (unused while reward_ema
-    is on, as in the reference)."""
+    is on, as in the reference; with defaults='dreamer_v2' -- passed on to dreamer_cfg -- it normalises the intrinsic reward)."""
     base = dict(grad_heads=['decoder'], actor_ent=0, reward_norm=dict(momentum=0.95, scale=1.0, eps=1e-8))
     base.update(over)
     return dreamer_cfg(batch_size, batch_length, device, task, **base)

@@ -2292,3 +2292,140 @@ class _EnsVar(Function):
 
 def ens_var(preds):
     return _EnsVar.apply(preds)
+
+
+# ------------------------------------------------------------------ the DreamerV2 defaults (csrc/normfree.hip): norm-free layers, truncated-normal actor, mse heads
+
+def silu_fwd_raw(x, y, M, N, P=None):
+    """y = x sigmoid(x) over M contiguous rows of N floats (y may be x); P: planes of y"""
+    check(lib().genrl_silu_fwd_h2(_p(x), N, _p(y), N, M, N, *_plane_out(P), _stream()), 'silu_fwd_h2')
+
+
+def silu_bwd_raw(dy, x, dx, M, N, P=None):
+    """dx = dy silu'(x) from the saved pre-activation x (dx may be dy); P: planes of dx"""
+    check(lib().genrl_silu_bwd_h2(_p(dy), N, _p(x), N, _p(dx), N, M, N, *_plane_out(P), _stream()), 'silu_bwd_h2')
+
+
+class _DenseAct(Function):
+    """y = SiLU([x1, x2] W^T): Linear without bias + NormLayer('none') + act (agent/dreamer_utils.py:739-747 with `norm: none`,
+    conf/defaults/dreamer_v2.yaml) as one autograd node on fp32 operands; the layout of _DenseLNAct without the LayerNorm."""
+    @staticmethod
+    def forward(ctx, x1, x2, W):
+        a = _f32(x1).reshape(-1, x1.shape[-1]).contiguous()
+        c = _f32(x2).reshape(-1, x2.shape[-1]).contiguous() if x2 is not None else None
+        M, K1 = a.shape
+        K2 = c.shape[1] if c is not None else 0
+        N, K = W.shape
+        assert K == K1 + K2 and N % 4 == 0
+        pre = torch.empty(M, N, device=a.device)
+        w1, ld1 = _aligned_block(W, K1, M)
+        sgemm(a, K1, 1, w1, ld1, 1, pre, N, None, M, N, K1)
+        if c is not None:
+            sgemm(c, K2, 1, W, K, 1, pre, N, None, M, N, K2, accumulate=True, b_off=K1)
+        ctx.w1 = (w1, ld1)
+        y = torch.empty_like(pre)
+        silu_fwd_raw(pre, y, M, N)
+        ctx.save_for_backward(a, c if c is not None else a.new_empty(0), W, pre)
+        ctx.has2 = c is not None
+        ctx.shapes = (x1.shape, x2.shape if x2 is not None else None)
+        return y.reshape(*x1.shape[:-1], N)
+
+    @staticmethod
+    def backward(ctx, dy):
+        a, c, W, pre = ctx.saved_tensors
+        M, K1 = a.shape
+        K2 = c.shape[1] if ctx.has2 else 0
+        N, K = W.shape
+        dev = dy.device
+        dpre = torch.empty_like(pre)
+        silu_bwd_raw(_f32(dy).reshape(M, N).contiguous(), pre, dpre, M, N)
+        d1 = d2 = dW = None
+        if ctx.needs_input_grad[0]:
+            d1 = torch.empty(M, K1, device=dev)
+            sgemm(dpre, N, 1, ctx.w1[0], 1, ctx.w1[1], d1, K1, None, M, K1, N)
+            d1 = d1.reshape(ctx.shapes[0])
+        if ctx.has2 and ctx.needs_input_grad[1]:
+            d2 = torch.empty(M, K2, device=dev)
+            sgemm(dpre, N, 1, W, 1, K, d2, K2, None, M, K2, N, b_off=K1)
+            d2 = d2.reshape(ctx.shapes[1])
+        if ctx.needs_input_grad[2]:
+            tgt, acc, dW = _wgrad_target(W)
+            def wg():
+                sgemm(dpre, 1, N, a, 1, K1, tgt, K, None, N, K1, M, accumulate=acc)
+                if ctx.has2:
+                    sgemm(dpre, 1, N, c, 1, K2, tgt, K, None, N, K2, M, accumulate=acc, c_off=K1)
+            if acc:
+                wgrad_stream.run(wg, dpre, a, c)
+            else:
+                wg()
+        return d1, d2, dW
+
+
+def dense_act(x1, x2, W):
+    return _DenseAct.apply(x1, x2, W)
+
+
+class _TruncNormalHead(Function):
+    @staticmethod
+    def forward(ctx, raw, eps, min_std, init_std):
+        r2 = _f32(raw).reshape(-1, raw.shape[-1]).contiguous()
+        R, A2 = r2.shape
+        A = A2 // 2
+        e = _f32(eps).reshape(R, A).contiguous()
+        act = torch.empty(R, A, device=raw.device)
+        check(lib().genrl_trunc_normal_head_fwd(_p(r2), _p(e), _p(act), None, None, R, A, min_std, init_std, 0, _stream()),
+              'trunc_normal_head_fwd')
+        ctx.save_for_backward(r2, e)
+        ctx.cfg = (init_std, raw.shape)
+        return act.reshape(*raw.shape[:-1], A)
+
+    @staticmethod
+    def backward(ctx, g):
+        r2, e = ctx.saved_tensors
+        init_std, rshape = ctx.cfg
+        R, A2 = r2.shape
+        d = torch.empty_like(r2)
+        check(lib().genrl_trunc_normal_head_bwd(_p(_f32(g).reshape(R, A2 // 2).contiguous()), _p(r2), _p(e), _p(d), R, A2 // 2, init_std,
+                                                0, _stream()), 'trunc_normal_head_bwd')
+        return d.reshape(rshape), None, None, None
+
+
+def trunc_normal_sample(raw, eps, min_std=0.1, init_std=0.0):
+    """raw (..., 2A) = [out | std_raw] -> clamp(tanh(out) + std eps, -1 + 1e-6, 1 - 1e-6) with the straight-through gradient of
+    TruncatedNormal.sample (tools/utils.py:102-123)"""
+    return _TruncNormalHead.apply(raw, eps, float(min_std), float(init_std))
+
+
+def trunc_normal_mean_std(raw, min_std=0.1, init_std=0.0):
+    """-> tanh(out), 2 sigmoid((std_raw + init_std) / 2) + min_std (no gradient: acting, eval_policy, metrics)"""
+    r2 = _f32(raw.detach()).reshape(-1, raw.shape[-1]).contiguous()
+    R, A2 = r2.shape
+    A = A2 // 2
+    mean = torch.empty(R, A, device=raw.device); std = torch.empty(R, A, device=raw.device)
+    check(lib().genrl_trunc_normal_head_fwd(_p(r2), None, None, _p(mean), _p(std), R, A, min_std, init_std, 0, _stream()),
+          'trunc_normal_head_fwd')
+    return mean.reshape(*raw.shape[:-1], A), std.reshape(*raw.shape[:-1], A)
+
+
+class _SqErr(Function):
+    @staticmethod
+    def forward(ctx, out, x):
+        o = _f32(out).contiguous(); t = _f32(x).contiguous()
+        assert o.numel() == t.numel()
+        like = torch.empty_like(o)
+        check(lib().genrl_sqerr_fwd(_p(o), _p(t), _p(like), o.numel(), _stream()), 'sqerr_fwd')
+        ctx.save_for_backward(o, t)
+        return like
+
+    @staticmethod
+    def backward(ctx, g):
+        o, t = ctx.saved_tensors
+        d = torch.empty_like(o)
+        check(lib().genrl_sqerr_bwd(_p(o), _p(t), _p(_f32(g).contiguous()), _p(d), o.numel(), _stream()), 'sqerr_bwd')
+        return d, None
+
+
+def sqerr_like(out, x):
+    """MSEDist(out).log_prob(x) of a one-wide head: out, x (..., 1) -> -(out - x)^2 of shape (...)"""
+    assert out.shape[-1] == 1 and out.numel() == x.numel(), (out.shape, x.shape)
+    return _SqErr.apply(out, x.detach().reshape(out.shape)).squeeze(-1)

@@ -531,6 +531,97 @@ def dense_ln_act(x1, x2, W, b, gamma, beta, eps=1e-5, planes=None):
     return y
 
 
+class _DenseActPlanes(Function):
+    """ops._DenseAct (y = SiLU([x1, x2] W^T): a norm-free layer of conf/defaults/dreamer_v2.yaml) with plane operands: the product
+    runs on the inputs' planes (P1 / P2 with their first rows: a previous layer's output or a rollout's states; inputs that come without
+    are split here), genrl_silu_fwd_h2 writes the output's planes (out_p) for the next product, the backward's genrl_silu_bwd_h2 emits
+    the planes of the pre-activation gradient for the dgrad products (transposed weight planes) and, where planes.tn_ok holds, for the
+    weight gradient through genrl_gemm_h2_tn; below that the weight gradient stays on the fp32-operand kernels."""
+    @staticmethod
+    def forward(ctx, x1, x2, W, P1, r1, P2, r2, out_p):
+        a = _f32(x1).reshape(-1, x1.shape[-1]).contiguous()
+        c = _f32(x2).reshape(-1, x2.shape[-1]).contiguous() if x2 is not None else None
+        M, K1 = a.shape
+        K2 = c.shape[1] if c is not None else 0
+        N, K = W.shape
+        assert K == K1 + K2
+        if P1 is None:
+            P1, r1 = planes.split(a.detach()), 0
+        if c is not None and P2 is None:
+            P2, r2 = planes.split(c.detach()), 0
+        pre = torch.empty(M, N, device=a.device)
+        if c is None:
+            planes.gemm(P1, planes.weight(W), pre, N, None, M, N, a_row0=r1)
+        else:
+            planes.gemm(P1, planes.weight(W, c0=0, c1=K1), pre, N, None, M, N, a_row0=r1, A1=P2, B1=planes.weight(W, c0=K1), a1_row0=r2)
+        y = torch.empty_like(pre)
+        ops.silu_fwd_raw(pre, y, M, N, out_p)
+        ctx.save_for_backward(a, c if c is not None else a.new_empty(0), W, pre)
+        ctx.has2 = c is not None
+        keep = (ctx.needs_input_grad[2] and planes.tn_ok(M, N, K1, K) and (c is None or K2 % 4 == 0) and r1 % 4 == 0 and r2 % 4 == 0)
+        ctx.in_planes = ((P1, r1), (P2, r2)) if keep else None
+        ctx.shapes = (x1.shape, x2.shape if x2 is not None else None)
+        return y.reshape(*x1.shape[:-1], N)
+
+    @staticmethod
+    def backward(ctx, dy):
+        a, c, W, pre = ctx.saved_tensors
+        M, K1 = a.shape
+        K2 = c.shape[1] if ctx.has2 else 0
+        N, K = W.shape
+        dev = dy.device
+        ip = ctx.in_planes
+        dpre = torch.empty_like(pre)
+        dpre_p = planes.Planes(M, N, dev)
+        ops.silu_bwd_raw(_f32(dy).reshape(M, N).contiguous(), pre, dpre, M, N, dpre_p)
+        d1 = d2 = dW = None
+        if ctx.needs_input_grad[0]:
+            d1 = torch.empty(M, K1, device=dev)
+            planes.gemm(dpre_p, planes.weight(W, True, 0, K1), d1, K1, None, M, K1)
+            d1 = d1.reshape(ctx.shapes[0])
+        if ctx.has2 and ctx.needs_input_grad[1]:
+            d2 = torch.empty(M, K2, device=dev)
+            planes.gemm(dpre_p, planes.weight(W, True, K1), d2, K2, None, M, K2)
+            d2 = d2.reshape(ctx.shapes[1])
+        if ctx.needs_input_grad[2]:
+            tgt, acc, dW = _wgrad_target(W)
+            if ip is not None:
+                planes.gemm_tn(dpre_p, ip[0][0], tgt, K, N, K1, M, accumulate=acc, b_row0=ip[0][1])
+                if ctx.has2:
+                    planes.gemm_tn(dpre_p, ip[1][0], tgt, K, N, K2, M, accumulate=acc, b_row0=ip[1][1], c_off=K1)
+            else:
+                sgemm(dpre, 1, N, a, 1, K1, tgt, K, None, N, K1, M, accumulate=acc)
+                if ctx.has2:
+                    sgemm(dpre, 1, N, c, 1, K2, tgt, K, None, N, K2, M, accumulate=acc, c_off=K1)
+        return d1, d2, dW, None, None, None, None, None
+
+
+def _input_planes(x1, x2, planes_):
+    """the (Planes, first row) handles dense_ln_act / dense_act take for their inputs: the caller's, or the inputs' own `_planes`
+    attribute (a previous layer's output); dropped where they do not cover the rows"""
+    M = x1.numel() // x1.shape[-1]
+    if planes_ is None:
+        h1 = getattr(x1, '_planes', None)
+        h2 = getattr(x2, '_planes', None) if x2 is not None else None
+    else:
+        h1, h2 = planes_[0], (planes_[1] if len(planes_) > 1 else None)
+    if h1 is not None and (h1[0].cols != x1.shape[-1] or h1[1] + M > h1[0].rows):
+        h1 = None
+    if x2 is not None and h2 is not None and (h2[0].cols != x2.shape[-1] or h2[1] + M > h2[0].rows):
+        h2 = None
+    return (h1 if h1 is not None else (None, 0)), (h2 if h2 is not None else (None, 0))
+
+
+def dense_act(x1, x2, W, planes=None):
+    """-> y = SiLU([x1, x2] W^T) with y._planes = (planes of y, 0) for the next layer; `planes` as dense_ln_act's"""
+    M = x1.numel() // x1.shape[-1]
+    (P1, r1), (P2, r2) = _input_planes(x1, x2, planes)
+    out_p = pl.Planes(M, W.shape[0], x1.device)
+    y = _DenseActPlanes.apply(x1, x2, W, P1, r1, P2, r2, out_p)
+    y._planes = (out_p, 0)
+    return y
+
+
 def imagine_rollout(stoch0, deter0, logit0, eps, q, spec):
     tape = spec.tape
     flat = [qq for l in tape.layers for qq in l[:4]]

@@ -619,6 +619,27 @@ int genrl_ens_var_fwd(const float* p, long member, long ld, int K, float* r, int
 int genrl_ens_var_bwd(const float* g, const float* p, long member, long ld, int K, float* dp, long dmember, long lddp, int M, int N,
                       uint16_t* dpp, long pmember, long ldpl, long plane, float* inv, long imember, void* stream);
 
+/* ---- the DreamerV2 defaults (conf/defaults/dreamer_v2.yaml; genrl_amd/csrc/normfree.hip)
+ * genrl_silu_{fwd,bwd}_h2: the activation behind a Linear without LayerNorm (`norm: none`, agent/dreamer_utils.py:739-747).  Rows, pitches,
+ *   alignment and the optional plane output as genrl_relu_*_h2 above (planes bit-identical to genrl_split_h2 of the fp32 output).
+ *   fwd: y = x sigmoid(x) (y may be x).  bwd: dx = dy sigmoid(x) (1 + x (1 - sigmoid(x))) from the saved pre-activation x (dx may be dy).
+ *   Large |x| gives no NaN (x = -100: y = -0, dx = -0 dy); a NaN input stays NaN.
+ * genrl_trunc_normal_head_{fwd,bwd}: DistLayer 'trunc_normal' (:830-834) + TruncatedNormal.sample (tools/utils.py:102-123) on
+ *   raw [R, 2A] = [out | std_raw]: mean = tanh(out), std = 2 sigmoid((std_raw + init_std) / 2) + min_std, action = clamp(mean + eps std,
+ *   -1 + 1e-6, 1 - 1e-6) (rows ld_action apart, 0 = A).  eps NULL: the mean-only form (action, if given, = clamp(mean)); any of action / mean /
+ *   std may be NULL.  bwd: the clamp is straight-through -- d raw is that of mean + eps std for every element, clamped or not.
+ * genrl_sqerr_{fwd,bwd}: MSEDist.log_prob of a one-wide head (:62-83): like = -(out - x)^2 elementwise; dout = -2 (out - x) g. */
+int genrl_silu_fwd_h2(const float* x, long ldx, float* y, long ldy, int M, int N, uint16_t* yp, long ldp, long plane, float* inv,
+                      void* stream);
+int genrl_silu_bwd_h2(const float* dy, long lddy, const float* x, long ldx, float* dx, long lddx, int M, int N, uint16_t* dxp, long ldp,
+                      long plane, float* inv, void* stream);
+int genrl_trunc_normal_head_fwd(const float* raw, const float* eps, float* action, float* mean, float* std, long R, int A,
+                                float min_std, float init_std, long ld_action, void* stream);
+int genrl_trunc_normal_head_bwd(const float* daction, const float* raw, const float* eps, float* draw, long R, int A, float init_std,
+                                long ld_action, void* stream);
+int genrl_sqerr_fwd(const float* out, const float* x, float* like, long n, void* stream);
+int genrl_sqerr_bwd(const float* out, const float* x, const float* g, float* dout, long n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
