@@ -325,14 +325,22 @@ class WorldModel(Module):  # ref :120-321
         N = start['deter'].shape[0]
         dev = start['deter'].device
         A = policy._out._out.out_features
-        eps = noise.draw('normal', 'imag.act_eps', (horizon, N, A), dev) if not eval_policy else None
+        # the policy's head by its distribution: DistLayer 'normal' (dreamer_v3 / genrl defaults), 'trunc_normal' (dreamer_v2) or 'onehot'
+        # (`discrete_actions`; its draws are exponential-race noise from a site of their own)
+        onehot = policy._out._dist == 'onehot'
+        if onehot:
+            eps = noise.draw('exp', 'imag.act_q', (horizon, N, A), dev) if not eval_policy else None
+        else:
+            eps = noise.draw('normal', 'imag.act_eps', (horizon, N, A), dev) if not eval_policy else None
         q = noise.draw('exp', 'imag.step_q', (horizon, N * self.rssm._stoch, self.rssm._discrete), dev)
         rssm = self.rssm
         seq = {k: [v] for k, v in start.items()}
         seq['action'] = [torch.zeros(N, A, device=dev)]
-        # the policy's head by its distribution: DistLayer 'normal' (dreamer_v3 / genrl defaults) or 'trunc_normal' (dreamer_v2)
         trunc = policy._out._dist == 'trunc_normal'
-        if trunc:
+        if onehot:          # eval_policy: the mixed probabilities (OneHotDist.mean, ref :266); the reference's throw-away sample (ref :259-260) stays dropped
+            head_mean = ops.onehot_probs
+            head_sample = ops.onehot_sample
+        elif trunc:
             head_mean = lambda raw: ops.trunc_normal_mean_std(raw, policy._out._min_std, policy._out._init_std)[0]
             head_sample = lambda raw, e: ops.trunc_normal_sample(raw, e, policy._out._min_std, policy._out._init_std)
         else:
@@ -340,15 +348,18 @@ class WorldModel(Module):  # ref :120-321
             head_mean = lambda raw: ops.actor_mean_std(raw, policy._out._min_std, policy._out._max_std)[0]
             head_sample = lambda raw, e: ops.actor_sample(raw, e, policy._out._min_std, policy._out._max_std)
         # the two heads of DistLayer('normal' / 'trunc_normal') (mean, std) as ONE product: weights stacked once per rollout
-        head_w = torch.cat([policy._out._out.weight, policy._out._std.weight], 0)
-        head_b = torch.cat([policy._out._out.bias, policy._out._std.bias], 0)
+        if onehot:
+            head_w, head_b = policy._out._out.weight, policy._out._out.bias
+        else:
+            head_w = torch.cat([policy._out._out.weight, policy._out._std.weight], 0)
+            head_b = torch.cat([policy._out._out.bias, policy._out._std.bias], 0)
         raws = []
         # training rollouts: the policy's H backward passes are batched into one over all H*N rows
         # (the tape, the fused rollout and their C launch loops have the LayerNorm launches and the Normal head built in: a norm-free
-        # world model or policy, or a truncated-normal head, takes the step-by-step loop below)
+        # world model or policy, or a truncated-normal or one-hot head, takes the step-by-step loop below)
         tape = None
         if (torch.is_grad_enabled() and head_w.requires_grad and horizon > 1 and policy._norm != 'none' and rssm._norm != 'none'
-                and not trunc):
+                and not trunc and not onehot):
             layers = [(getattr(policy, f'dense{i}').weight, getattr(policy, f'dense{i}').bias,
                        getattr(policy, f'norm{i}')._layer.weight, getattr(policy, f'norm{i}')._layer.bias,
                        getattr(policy, f'norm{i}')._layer.eps) for i in range(policy._layers)]
@@ -393,7 +404,7 @@ class WorldModel(Module):  # ref :120-321
                 tape.inputs = (seq['stoch'].detach().reshape(horizon + 1, N, -1), seq['deter'].detach())
             # policy outputs at states 0..H-1 — exactly what ActorCritic.actor_loss re-evaluates for its
             # entropy metric (agent/dreamer.py:397: actor(sg(feat[:-2]))): kept to avoid a second forward
-            self._last_actor_raw = torch.stack(raws, 0)          # (H, N, 2A), attached to the actor's graph
+            self._last_actor_raw = torch.stack(raws, 0)          # (H, N, 2A) -- one-hot head: the logits (H, N, A) --, attached to the actor's graph
         seq = _ImaginedSeq(rssm, seq)                  # 'feat' = cat(stoch, deter) (ref :272) on first access
         seq.planes = locals().get('state_planes')          # (planes of stoch / deter, rows h*N + n, from the fused rollout)
         # no discount head (conf/env/dmc_pixels.yaml:6): discount = gamma everywhere and weight = cumprod(ones) = 1
@@ -434,9 +445,13 @@ class ActorCritic(Module):  # ref :323-462
         self.act_spec = act_spec
         self._use_amp = (config.precision == 16)
         self.device = config.device
-        assert not getattr(self.cfg, 'discrete_actions', False)
+        if getattr(self.cfg, 'discrete_actions', False):          # ref :332-333
+            self.cfg.actor.dist = 'onehot'
         self.actor_grad = getattr(self.cfg, f'{self.name}_actor_grad'.strip('_'))
-        assert self.actor_grad == 'dynamics', 'GenRL trains the actor through the dynamics'
+        if self.actor_grad not in ('dynamics', 'reinforce'):      # ref :413-419
+            raise NotImplementedError(self.actor_grad)
+        if self.actor_grad == 'reinforce' and self.cfg.actor.dist != 'onehot':
+            raise NotImplementedError('actor_grad reinforce is implemented for the one-hot head of discrete_actions')
         self.actor = common.MLP(feat_size, act_spec.shape[0], **self.cfg.actor)
         self.critic = common.MLP(feat_size, (1,), **self.cfg.critic)
         assert self.cfg.slow_target
@@ -507,7 +522,44 @@ class ActorCritic(Module):  # ref :323-462
             self.update_slow_target()
         return {f'{self.name}_{k}'.strip('_'): v for k, v in metrics.items()}
 
-    def actor_loss(self, seq, target, baseline):  # ref :392-429 (actor_grad 'dynamics')
+    def _policy_raw(self, seq):
+        """The actor head's raw outputs at the rollout's states 0 .. H-2 (ref :397: actor(sg(feat[:-2])))"""
+        n_pol = seq['stoch'].shape[0] - 2
+        raw = getattr(self, '_rollout_actor_raw', None)
+        if raw is None or raw.shape[0] < n_pol:       # rollout not produced by WorldModel.imagine: re-evaluate
+            s, d = stop_gradient(seq['stoch'][:-2]), stop_gradient(seq['deter'][:-2])
+            raw = self.actor._out.raw(self.actor.trunk(s.reshape(list(s.shape[:-2]) + [-1]), d))
+        # same weights, same inputs as the rollout's own policy evaluations (the reference re-runs the
+        # actor on sg(feat[:-2]), ref :397): their outputs - and graph - are reused
+        return raw[:n_pol]
+
+    def _reinforce_loss(self, seq, target, baseline):
+        """ref :392-429 with actor_grad 'reinforce' on the one-hot head: log-probability of the taken actions and entropy from the
+        rollout's own logits (one launch), then normalisation, advantage, entropy bonus, weighted mean and sign as one node.  The
+        advantage is not detached in the reference (ref :416-417): target and baseline receive their gradients too and carry them
+        back into the rollout through the straight-through action samples.  The objective is a fresh tensor there (ref :417), so
+        the critic regresses onto the untouched lambda-returns whatever `reward_ema` says."""
+        metrics = {}
+        ent_scale = self.cfg.actor_ent
+        last = None
+        if self.cfg.reward_ema:
+            offset, scale = self.reward_ema(target, self.ema_vals)
+            last = getattr(self.reward_ema, 'last', None)
+            if last is None:
+                last = torch.stack([offset, scale]).float()
+        logp, ent = ops.onehot_logp_ent(self._policy_raw(seq), stop_gradient(seq['action'][1:-1]))
+        weight = None if getattr(seq, 'unit_weight', False) else stop_gradient(seq['weight'])[:-2]
+        actor_loss, st = ops.reinforce_objective(target, baseline, logp, ent, weight, last, ent_scale)
+        if last is not None:
+            metrics['normed_target_mean'], metrics['normed_target_std'] = st[0], st[1]
+            metrics['reward_ema_005'], metrics['reward_ema_095'] = self.ema_vals[0], self.ema_vals[1]
+        metrics['actor_ent'] = ops.wmean(ent.detach(), None, 1.0)
+        metrics['actor_ent_scale'] = ent_scale
+        return actor_loss, metrics
+
+    def actor_loss(self, seq, target, baseline):  # ref :392-429
+        if self.actor_grad == 'reinforce':
+            return self._reinforce_loss(seq, target, baseline)
         metrics = {}
         ent_scale = self.cfg.actor_ent
         weight = stop_gradient(seq['weight'])
@@ -530,18 +582,19 @@ class ActorCritic(Module):  # ref :323-462
             metrics['reward_ema_005'] = self.ema_vals[0].clone()
             metrics['reward_ema_095'] = self.ema_vals[1].clone()
             objective = normed_target[1:]
-        n_pol = seq['stoch'].shape[0] - 2
-        raw = getattr(self, '_rollout_actor_raw', None)
-        if raw is None or raw.shape[0] < n_pol:       # rollout not produced by WorldModel.imagine: re-evaluate
-            s, d = stop_gradient(seq['stoch'][:-2]), stop_gradient(seq['deter'][:-2])
-            raw = self.actor._out.raw(self.actor.trunk(s.reshape(list(s.shape[:-2]) + [-1]), d))
-        # same weights, same inputs as the rollout's own policy evaluations (the reference re-runs the
-        # actor on sg(feat[:-2]), ref :397): their outputs - and graph - are reused
-        raw = raw[:n_pol]
+        raw = self._policy_raw(seq)
         A = raw.shape[-1] // 2
         mn, mx = self.actor._out._min_std, self.actor._out._max_std
         trunc = self.actor._out._dist == 'trunc_normal'
-        if ent_scale != 0 or trunc:
+        if self.actor._out._dist == 'onehot':       # `discrete_actions`: the entropy of the unimix categorical over the logits
+            with contextlib.nullcontext() if ent_scale != 0 else torch.no_grad():
+                ent = ops.onehot_logp_ent(raw, None)[1][:, :, None]
+            if ent_scale != 0:
+                objective = objective + ent_scale * ent
+                if not ema:         # (the in-place `objective += ent_scale * ent` on a view of the returns: see below)
+                    self._critic_target = torch.cat([target[:1], objective], 0).detach()
+            metrics['actor_ent'] = ops.wmean(ent.detach(), None, 1.0)
+        elif ent_scale != 0 or trunc:
             # (the entropy of the untruncated Normal in both cases; with a truncated-normal head and scale 0 it is a metric only)
             with contextlib.nullcontext() if ent_scale != 0 else torch.no_grad():
                 if trunc:           # ref dreamer_utils.py:832

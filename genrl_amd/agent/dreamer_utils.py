@@ -109,10 +109,13 @@ class TwoHotDist:
 
 
 class OneHotDist:
-    """ref :177-197 wrapped in Independent(.,1) (ref :413-415): unimix categorical latents."""
-    def __init__(self, logits, site='onehot'):
+    """ref :177-197 wrapped in Independent(.,1) (ref :413-415): unimix categorical latents.  independent=False: the bare OneHotDist of
+    DistLayer 'onehot' (ref :835-836), the policy of a discrete-action actor -- one categorical per row, with log_prob; `site` names the
+    noise site its draws come from."""
+    def __init__(self, logits, site='onehot', independent=True):
         self.logits_raw = logits
         self.site = site
+        self.independent = independent
 
     def sample(self, sample_shape=()):
         lg = self.logits_raw
@@ -131,9 +134,17 @@ class OneHotDist:
 
     @property
     def mean(self):          # OneHotCategorical.mean; train.py:297 stores it as the start 'logit' of data-free rollouts
+        if not self.independent:        # (the action DreamerAgent.act returns in eval mode, agent/dreamer.py:54-59)
+            return ops.onehot_probs(self.logits_raw)
         return self.probs
 
+    def log_prob(self, action):
+        assert not self.independent, 'log_prob is implemented for the policy head only'
+        return ops.onehot_logp_ent(self.logits_raw, action)[0]
+
     def entropy(self):
+        if not self.independent:
+            return ops.onehot_logp_ent(self.logits_raw, None)[1]
         return ops.cat_entropy(self.logits_raw)
 
 
@@ -346,7 +357,7 @@ class DistLayer(Module):  # ref :787-841
         if self._dist == 'mse':
             return MSEHeadDist(raw.reshape(list(inputs.shape[:-1]) + list(self._shape)))
         if self._dist == 'onehot':
-            return OneHotDist(raw)
+            return OneHotDist(raw.float(), site='actor', independent=False)
         raise NotImplementedError(self._dist)
 
 

@@ -785,6 +785,110 @@ def actor_objective(target, weight, offset_scale):
     return _ActorObjective.apply(target, weight, offset_scale)
 
 
+# ------------------------------------------------------------------ discrete actions (discrete.hip)
+
+class _OneHotLogpEnt(Function):
+    @staticmethod
+    def forward(ctx, logits, action):
+        ctx.set_materialize_grads(False)
+        lg = _f32(logits).contiguous()
+        K = lg.shape[-1]
+        G = lg.numel() // K
+        ac = _f32(action.detach()).contiguous() if action is not None else None
+        assert ac is None or ac.shape == lg.shape, (ac.shape, lg.shape)
+        logp = torch.empty(lg.shape[:-1], device=lg.device) if ac is not None else None
+        ent = torch.empty(lg.shape[:-1], device=lg.device)
+        check(lib().genrl_onehot_logp_ent_fwd(_p(lg), _p(ac), _p(logp), _p(ent), G, K, 1.0 - UNIMIX, _stream()), 'onehot_logp_ent_fwd')
+        ctx.save_for_backward(lg, ac)
+        if logp is None:
+            logp = ent.new_zeros(())
+            ctx.mark_non_differentiable(logp)
+        return logp, ent
+
+    @staticmethod
+    def backward(ctx, glogp, gent):
+        lg, ac = ctx.saved_tensors
+        if ac is None:
+            glogp = None
+        if glogp is None and gent is None:
+            return None, None
+        K = lg.shape[-1]
+        d = torch.empty_like(lg)
+        check(lib().genrl_onehot_logp_ent_bwd(_p(lg), _p(ac) if glogp is not None else None,
+                                              _p(glogp.contiguous()) if glogp is not None else None,
+                                              _p(gent.contiguous()) if gent is not None else None, _p(d), lg.numel() // K, K,
+                                              1.0 - UNIMIX, 0, _stream()), 'onehot_logp_ent_bwd')
+        return d, None
+
+
+class _OneHotProbs(Function):
+    @staticmethod
+    def forward(ctx, logits):
+        lg = _f32(logits).contiguous()
+        K = lg.shape[-1]
+        mode, probs = torch.empty_like(lg), torch.empty_like(lg)
+        check(lib().genrl_onehot_fwd(_p(lg), None, _p(mode), _p(probs), lg.numel() // K, K, UNIMIX, _stream()), 'onehot_fwd')
+        ctx.save_for_backward(lg)
+        return probs
+
+    @staticmethod
+    def backward(ctx, g):                      # (the straight-through gradient of a sample IS d probs / d logits)
+        return _OneHotSample.backward(ctx, g)[0]
+
+
+def onehot_probs(logits):
+    """OneHotDist(logits).mean: the class probabilities after the uniform mix, from the sampling kernel's own arithmetic"""
+    return _OneHotProbs.apply(logits)
+
+
+def onehot_logp_ent(logits, action):
+    """OneHotDist(logits) of a discrete-action actor: -> (log_prob(action), entropy()), both of logits.shape[:-1]; gradient to the
+    logits only (the reference evaluates log_prob on sg(action)).  action None: the entropy alone (log_prob comes back as a 0 scalar)."""
+    return _OneHotLogpEnt.apply(logits, action)
+
+
+class _ReinforceObjective(Function):
+    @staticmethod
+    def forward(ctx, target, baseline, logp, ent, weight, os, ent_scale):
+        t = _f32(target).contiguous(); b = _f32(baseline).contiguous()
+        H = t.shape[0]
+        N = t.numel() // H
+        assert b.numel() == H * N, (b.shape, t.shape)
+        lp = _f32(logp).contiguous(); en = _f32(ent).contiguous()
+        assert lp.numel() == (H - 1) * N and en.numel() == (H - 1) * N, (lp.shape, en.shape, t.shape)
+        w = _f32(weight.detach()).reshape(-1).contiguous() if weight is not None else None
+        assert w is None or w.numel() == (H - 1) * N
+        loss, out = torch.empty((), device=t.device), torch.zeros(2, device=t.device)
+        check(lib().genrl_reinforce_obj_fwd(_p(t), _p(b), _p(lp), _p(en), _p(w), _p(os), ent_scale, H, N, _p(loss), _p(out),
+                                            _stream()), 'reinforce_obj_fwd')
+        ctx.save_for_backward(t, b, lp, os)
+        ctx.w, ctx.dims, ctx.ent_scale = w, (H, N), ent_scale
+        ctx.shapes = (target.shape, baseline.shape, logp.shape, ent.shape)
+        ctx.mark_non_differentiable(out)
+        return loss, out
+
+    @staticmethod
+    def backward(ctx, g, _g2):
+        t, b, lp, os = ctx.saved_tensors
+        H, N = ctx.dims
+        need = ctx.needs_input_grad
+        dev = g.device
+        dt = torch.empty(ctx.shapes[0], device=dev) if need[0] else None
+        db = torch.empty(ctx.shapes[1], device=dev) if need[1] else None
+        dl = torch.empty(ctx.shapes[2], device=dev) if need[2] else None
+        de = torch.empty(ctx.shapes[3], device=dev) if need[3] else None
+        check(lib().genrl_reinforce_obj_bwd(_p(g.contiguous()), _p(t), _p(b), _p(lp), _p(ctx.w), _p(os), ctx.ent_scale, H, N,
+                                            _p(dl), _p(dt), _p(db), _p(de), _stream()), 'reinforce_obj_bwd')
+        return dt, db, dl, de, None, None, None
+
+
+def reinforce_objective(target, baseline, logp, ent, weight=None, offset_scale=None, ent_scale=0.0):
+    """-> (loss, stats[2]): agent/dreamer.py:400-429 with actor_grad 'reinforce' as one node.  target, baseline (H, N[, 1]); logp, ent
+    (H-1, N[, 1]); weight (H-1, N[, 1]) or None; offset_scale: quantile_ema's output, or None without the return EMA (stats then 0).
+    The advantage is not detached: gradients reach target and baseline as well as logp and ent."""
+    return _ReinforceObjective.apply(target, baseline, logp, ent, weight, offset_scale, float(ent_scale))
+
+
 # ------------------------------------------------------------------ MSE image likelihood
 
 class _MSELike(Function):

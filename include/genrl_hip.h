@@ -640,6 +640,29 @@ int genrl_trunc_normal_head_bwd(const float* daction, const float* raw, const fl
 int genrl_sqerr_fwd(const float* out, const float* x, float* like, long n, void* stream);
 int genrl_sqerr_bwd(const float* out, const float* x, const float* g, float* dout, long n, void* stream);
 
+/* ---- discrete actions (`discrete_actions`, agent/dreamer.py:332-333; `actor_grad: reinforce`, :413-419; genrl_amd/csrc/discrete.hip)
+ * genrl_onehot_logp_ent_{fwd,bwd}: the actor's OneHotDist (agent/dreamer_utils.py:177-197) on logits [G, K], 2 <= K <= 64 (returns 1
+ *   otherwise and writes nothing): p = (1 - unimix) softmax(logits) + unimix / K, renormalised as torch's Categorical(probs=) does.  Here
+ *   `unimix` is the weight of the UNIFORM part (0.01), not the 0.99 that genrl_onehot_fwd takes.  logp[g] = sum_k action[g, k] log p[g, k]
+ *   (action: one-hot rows [G, K]), ent[g] = -sum_k p log p, with log p = log(clamp(p, eps, 1 - eps)) (probs_to_logits); logp or ent may
+ *   be NULL.  bwd: dlogits = glogp[g] d logp + gent[g] d ent through the mix and the softmax (glogp or gent may be NULL; accumulate != 0
+ *   adds into dlogits, as genrl_onehot_bwd does).  No gradient to action.
+ * genrl_reinforce_obj_{fwd,bwd}: the REINFORCE actor objective with the shapes and conventions of genrl_actor_obj_*: target, baseline
+ *   [H, N] (row 0 unused), logp, ent, weight [H-1, N] (weight may be NULL = 1; ent may be NULL when ent_scale == 0), offset_scale =
+ *   genrl_quantile_ema's out (NULL: `reward_ema: False`, offset 0, scale 1):
+ *     loss[0] = -mean(weight (logp ((target[1:] - offset) / scale - (baseline[1:] - offset) / scale) + ent_scale ent));
+ *   with offset_scale, out = (mean, unbiased std of (target - offset) / scale over all H N).  bwd, from the scalar gradient g: dlogp, dent
+ *   [H-1, N], dtarget, dbaseline [H, N] with row 0 zero (any of them may be NULL).  The advantage is NOT detached (:416-417). */
+int genrl_onehot_logp_ent_fwd(const float* logits, const float* action, float* logp, float* ent, long G, int K, float unimix,
+                              void* stream);
+int genrl_onehot_logp_ent_bwd(const float* logits, const float* action, const float* glogp, const float* gent, float* dlogits,
+                              long G, int K, float unimix, int accumulate, void* stream);
+int genrl_reinforce_obj_fwd(const float* target, const float* baseline, const float* logp, const float* ent, const float* weight,
+                            const float* offset_scale, float ent_scale, int H, long N, float* loss, float* out, void* stream);
+int genrl_reinforce_obj_bwd(const float* g, const float* target, const float* baseline, const float* logp, const float* weight,
+                            const float* offset_scale, float ent_scale, int H, long N, float* dlogp, float* dtarget,
+                            float* dbaseline, float* dent, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
