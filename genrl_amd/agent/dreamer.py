@@ -148,6 +148,12 @@ def _constant(shape, value, dev):
     return _constants[key]
 
 
+def _flat_stoch(stoch, deter):
+    """the latent of rollout states as rows of features, with deter's leading dimensions: (..., S, K) one-hot latents -> (..., S K);
+    continuous latents (..., S) as they are"""
+    return stoch.reshape(list(deter.shape[:-1]) + [-1])
+
+
 def _state_planes(seq):
     """((stoch planes, 0), (deter planes, 0)) of an imagined sequence whose rollout produced them, else None"""
     p_ = getattr(seq, 'planes', None)
@@ -332,8 +338,12 @@ class WorldModel(Module):  # ref :120-321
             eps = noise.draw('exp', 'imag.act_q', (horizon, N, A), dev) if not eval_policy else None
         else:
             eps = noise.draw('normal', 'imag.act_eps', (horizon, N, A), dev) if not eval_policy else None
-        q = noise.draw('exp', 'imag.step_q', (horizon, N * self.rssm._stoch, self.rssm._discrete), dev)
         rssm = self.rssm
+        gauss = not rssm._discrete          # continuous latents: N(0, 1) noise for the reparameterised samples, one slice per step
+        if gauss:
+            step_eps = noise.draw('normal', 'imag.step_eps', (horizon, N, rssm._stoch), dev)
+        else:
+            q = noise.draw('exp', 'imag.step_q', (horizon, N * self.rssm._stoch, self.rssm._discrete), dev)
         seq = {k: [v] for k, v in start.items()}
         seq['action'] = [torch.zeros(N, A, device=dev)]
         trunc = policy._out._dist == 'trunc_normal'
@@ -356,10 +366,11 @@ class WorldModel(Module):  # ref :120-321
         raws = []
         # training rollouts: the policy's H backward passes are batched into one over all H*N rows
         # (the tape, the fused rollout and their C launch loops have the LayerNorm launches and the Normal head built in: a norm-free
-        # world model or policy, or a truncated-normal or one-hot head, takes the step-by-step loop below)
+        # world model or policy, or a truncated-normal or one-hot head, takes the step-by-step loop below; so do continuous latents, which
+        # the tape's state planes and the fused rollout's categorical sample know nothing of)
         tape = None
         if (torch.is_grad_enabled() and head_w.requires_grad and horizon > 1 and policy._norm != 'none' and rssm._norm != 'none'
-                and not trunc and not onehot):
+                and not trunc and not onehot and not gauss):
             layers = [(getattr(policy, f'dense{i}').weight, getattr(policy, f'dense{i}').bias,
                        getattr(policy, f'norm{i}')._layer.weight, getattr(policy, f'norm{i}')._layer.bias,
                        getattr(policy, f'norm{i}')._layer.eps) for i in range(policy._layers)]
@@ -395,9 +406,12 @@ class WorldModel(Module):  # ref :120-321
                 action = head_mean(raw) if eval_policy else head_sample(raw, eps[h])
                 x = common._dense_ln_silu(s_flat, rssm._img_in[0], rssm._img_in[1], action)
                 deter = ops.gru_step(x, deter, rssm._cell._layer.weight, rssm._cell._norm.weight, rssm._cell._norm.bias)
-                logit = rssm._prior_logits(deter)
-                stoch = ops.onehot_sample(logit, q[h])
-                for key, value in dict(stoch=stoch, deter=deter, logit=logit, action=action).items():
+                if gauss:       # (whatever keys the state has are carried: mean and std beside stoch and deter)
+                    stoch, stats = rssm._gauss_stats(rssm._prior_raw(deter), True, 'imag.step_eps', step_eps[h])
+                else:
+                    logit = rssm._prior_logits(deter)
+                    stoch, stats = ops.onehot_sample(logit, q[h]), {'logit': logit}
+                for key, value in dict(stoch=stoch, deter=deter, action=action, **stats).items():
                     seq[key].append(value)
             seq = {k: torch.stack(v, 0) for k, v in seq.items()}
             if tape is not None:     # layer-0 inputs of all steps = the stacked rollout states (no copies)
@@ -528,7 +542,7 @@ class ActorCritic(Module):  # ref :323-462
         raw = getattr(self, '_rollout_actor_raw', None)
         if raw is None or raw.shape[0] < n_pol:       # rollout not produced by WorldModel.imagine: re-evaluate
             s, d = stop_gradient(seq['stoch'][:-2]), stop_gradient(seq['deter'][:-2])
-            raw = self.actor._out.raw(self.actor.trunk(s.reshape(list(s.shape[:-2]) + [-1]), d))
+            raw = self.actor._out.raw(self.actor.trunk(_flat_stoch(s, d), d))
         # same weights, same inputs as the rollout's own policy evaluations (the reference re-runs the
         # actor on sg(feat[:-2]), ref :397): their outputs - and graph - are reused
         return raw[:n_pol]
@@ -621,7 +635,7 @@ class ActorCritic(Module):  # ref :323-462
 
     def critic_loss(self, seq, target):  # ref :431-438
         s, d = seq['stoch'][:-1], seq['deter'][:-1]
-        dist = self.critic(s.reshape(list(s.shape[:-2]) + [-1]), d, planes=_state_planes(seq))
+        dist = self.critic(_flat_stoch(s, d), d, planes=_state_planes(seq))
         target = stop_gradient(target)
         weight = stop_gradient(seq['weight'])
         # -(log_prob * weight).mean() as one node (ops.wmean)
@@ -633,7 +647,7 @@ class ActorCritic(Module):  # ref :323-462
     def target(self, seq):  # ref :440-453
         reward, disc = seq['reward'], seq['discount']
         s = seq['stoch']
-        value = self._target_critic(s.reshape(list(s.shape[:-2]) + [-1]), seq['deter'], planes=_state_planes(seq)).mean
+        value = self._target_critic(_flat_stoch(s, seq['deter']), seq['deter'], planes=_state_planes(seq)).mean
         # lambda_return(reward[:-1], value[:-1], bootstrap=value[-1]) (ref :446-449) on the unsliced tensors: the
         # slices + re-concatenation are three copies forward and three backward otherwise
         assert not isinstance(self.cfg.discount, torch.Tensor)

@@ -6,8 +6,8 @@ pickled agents are interchangeable; every forward/backward runs in the hand-writ
 of libgenrl_hip.so (genrl_amd/ops.py).  nn.Module containers (nn.Linear, nn.Conv2d, nn.LayerNorm)
 are used only as *parameter holders*: their torch forward is never called on the hot path.
 
-What the GenRL path and the dreamer_v3 / dreamer_v2 defaults configure is implemented (norm 'layer'/'none', act SiLU, discrete
-latents, GRU cell, dists mse / twohot / normal / trunc_normal / onehot, image_dist mse / normal_unit_std); other reference options raise.
+What the GenRL path and the dreamer_v3 / dreamer_v2 defaults configure is implemented (norm 'layer'/'none', act SiLU, discrete or
+continuous latents, GRU cell, dists mse / twohot / normal / trunc_normal / onehot, image_dist mse / normal_unit_std); other reference options raise.
 """
 import contextlib
 import re
@@ -152,6 +152,30 @@ def kl_divergence(p, q):
     return ops.cat_kl(p.logits_raw, q.logits_raw)
 
 
+class LatentNormalDist:
+    """Independent(Normal(mean, std), 1) of EnsembleRSSM.get_dist with `discrete: False` (ref :416-419), in the mould of OneHotDist: `sample`
+    is the reparameterised one (the reference binds it to rsample) and draws its noise at `site`.  (The training path does not come through
+    here: its samples are made from the head's raw output by ops.gauss_head, in the kernel that computes mean and std.)"""
+    def __init__(self, mean, std, site='normal'):
+        self._mean, self.std, self.site = mean, std, site
+
+    def sample(self, sample_shape=()):
+        eps = noise.draw('normal', self.site, tuple(self._mean.shape), self._mean.device)
+        return torch.addcmul(self._mean, self.std, eps)
+
+    rsample = sample
+
+    @property
+    def mean(self):
+        return self._mean
+
+    def mode(self):
+        return self._mean
+
+    def entropy(self):
+        return ops.gauss_entropy(self.std)
+
+
 class NormalDist:
     """Independent(Normal(tanh(out), std), 1) of DistLayer 'normal' (ref :814-819)."""
     def __init__(self, raw, min_std, max_std, site='actor'):
@@ -285,15 +309,17 @@ class ImgChLayerNorm(nn.Module):  # ref :1031-1040 (parameter holder; applied on
 def _dense_ln_silu(x, lin, norm, x2=None, planes=None):
     """Linear (+ second concatenated input) + LayerNorm + SiLU with the reference's layer objects.  planes: h2 planes of
     the inputs (genrl_amd/planes.py) when the caller has them.  NormLayer('none') (conf/defaults/dreamer_v2.yaml): Linear without
-    bias + SiLU (dense_act), under the same row threshold and switch."""
+    bias + SiLU (dense_act), under the same row threshold and switch.  A first input whose width is no multiple of 4 (continuous latents
+    with the reference's `stoch: 30`) stays on the fp32-operand kernels, whose scalar-load form takes any width and row spacing."""
     rows = x.numel() // x.shape[-1]
+    wide4 = x.shape[-1] % 4 == 0
     if norm._layer is None:
         assert lin.bias is None, 'a norm-free layer has no bias (ref :339-346, :734)'
-        if (pl.ENABLED and x.is_cuda and rows >= ops_planes.min_rows() and lin.weight.shape[0] % 4 == 0
+        if (pl.ENABLED and x.is_cuda and rows >= ops_planes.min_rows() and lin.weight.shape[0] % 4 == 0 and wide4
                 and os.environ.get('GENRL_PLANES_MLP', '1') != '0'):
             return ops_planes.dense_act(x, x2, lin.weight, planes=planes)
         return ops.dense_act(x, x2, lin.weight)
-    if (pl.ENABLED and x.is_cuda and rows >= ops_planes.min_rows() and lin.weight.shape[0] % 4 == 0
+    if (pl.ENABLED and x.is_cuda and rows >= ops_planes.min_rows() and lin.weight.shape[0] % 4 == 0 and wide4
             and os.environ.get('GENRL_PLANES_MLP', '1') != '0'):  # (-0.75 ms/step at c2 with the BK-64 128x128 tile, DESIGN 4a)
         return ops_planes.dense_ln_act(x, x2, lin.weight, lin.bias, norm._layer.weight, norm._layer.bias, norm._layer.eps,
                                    planes=planes)
@@ -499,13 +525,14 @@ class Decoder(Module):  # ref :631-715
 
 # ----------------------------------------------------------------------------- RSSM
 
-def _scan_noise(site, step_site, T, rows, K, dev):
-    """Exp(1) noise of a whole scan, (T, rows, K).  Tests that replay the reference's per-step draws inject them under the step
-    site's name (one tensor per obs_step call, `rssm.post` / `rssm.prior`): those are stacked in call order."""
+def _scan_noise(site, step_site, T, rows, K, dev, kind='exp'):
+    """Exp(1) noise (kind 'normal': N(0, 1), the continuous latents') of a whole scan, (T, rows, K).  Tests that replay the reference's
+    per-step draws inject them under the step site's name (one tensor per obs_step call, `rssm.post` / `rssm.prior`): those are stacked
+    in call order."""
     inj = noise._injected
     if inj is not None and site not in inj and step_site in inj:
-        return torch.stack([noise.draw('exp', step_site, (rows, K), dev) for _ in range(T)], 0)
-    return noise.draw('exp', site, (T, rows, K), dev)
+        return torch.stack([noise.draw(kind, step_site, (rows, K), dev) for _ in range(T)], 0)
+    return noise.draw(kind, site, (T, rows, K), dev)
 
 
 
@@ -515,18 +542,22 @@ class EnsembleRSSM(Module):  # ref :302-555
                  single_obs_posterior=False, cell_input='stoch', cell_type='gru'):
         super().__init__()
         assert action_dim is not None
-        assert discrete and ensemble == 1 and cell_type == 'gru' and cell_input == 'stoch' and norm in ('layer', 'none'), \
-            'discrete latents, ensemble 1, GRU, norm layer / none'
+        assert ensemble == 1 and cell_type == 'gru' and cell_input == 'stoch' and norm in ('layer', 'none'), \
+            'ensemble 1, GRU, norm layer / none'
+        assert discrete or std_act in ops.STD_ACTS, std_act      # (read by continuous latents only, ref :515-519)
         self.device = device
         self._embed_dim, self._action_dim, self._ensemble = embed_dim, action_dim, ensemble
         self._stoch, self._deter, self._hidden, self._discrete = stoch, deter, hidden, discrete
         self._norm, self._cell_type, self.cell_input = norm, cell_type, cell_input
+        self._std_act, self._min_std = std_act, min_std
         self.single_obs_posterior = single_obs_posterior
         self._cell = GRUCell(self._hidden, self._deter, norm=True, device=self.device)
-        self._ensemble_img_dist = nn.ModuleList([nn.Linear(hidden, stoch * discrete) for _ in range(ensemble)])
-        self._obs_dist = nn.Linear(hidden, stoch * discrete)
+        # discrete latents: S x K logits; continuous (`discrete` False / 0, ref :333-335): [mean | std_raw] of S Normal latents
+        stats = stoch * discrete if discrete else 2 * stoch
+        self._ensemble_img_dist = nn.ModuleList([nn.Linear(hidden, stats) for _ in range(ensemble)])
+        self._obs_dist = nn.Linear(hidden, stats)
         bias = norm != 'none'              # (a norm-free layer has no bias, ref :339-346; the GRU cell keeps its LayerNorm, ref :322)
-        self._img_in = nn.Sequential(nn.Linear(stoch * discrete + action_dim, hidden, bias=bias), NormLayer(norm, hidden))
+        self._img_in = nn.Sequential(nn.Linear(self.get_stoch_size() + action_dim, hidden, bias=bias), NormLayer(norm, hidden))
         self._ensemble_img_out = nn.ModuleList(
             [nn.Sequential(nn.Linear(deter, hidden, bias=bias), NormLayer(norm, hidden)) for _ in range(ensemble)])
         in_obs = embed_dim if single_obs_posterior else deter + embed_dim
@@ -535,11 +566,14 @@ class EnsembleRSSM(Module):  # ref :302-555
     # ---- shapes / helpers
     def initial(self, batch_size):
         z = lambda *s: _zeros(tuple(s), self.device)        # (read-only constants, built once per shape)
+        if not self._discrete:                              # ref :355-359
+            return dict(mean=z(batch_size, self._stoch), std=z(batch_size, self._stoch), stoch=z(batch_size, self._stoch),
+                        deter=self._cell.get_initial_state(None, batch_size))
         return dict(logit=z(batch_size, self._stoch, self._discrete), stoch=z(batch_size, self._stoch, self._discrete),
                     deter=self._cell.get_initial_state(None, batch_size))
 
     def get_stoch_size(self):
-        return self._stoch * self._discrete
+        return self._stoch * self._discrete if self._discrete else self._stoch
 
     def get_deter_size(self):
         return self._cell.state_size
@@ -549,6 +583,8 @@ class EnsembleRSSM(Module):  # ref :302-555
 
     def get_stoch(self, state):
         s = state['stoch']
+        if not self._discrete:
+            return s
         return s.reshape(list(s.shape[:-2]) + [self._stoch * self._discrete])
 
     def get_deter(self, state):
@@ -559,48 +595,75 @@ class EnsembleRSSM(Module):  # ref :302-555
 
     def get_dist(self, state, ensemble=False):
         assert not ensemble
+        if not self._discrete:
+            return LatentNormalDist(state['mean'].float(), state['std'].float())
         return OneHotDist(state['logit'].float())
 
     def get_unif_dist(self, state):
+        if not self._discrete:                              # N(0, 1), ref :427-429
+            return LatentNormalDist(torch.zeros_like(state['mean']), torch.ones_like(state['std']), site='rssm.unif')
         return OneHotDist(torch.ones_like(state['logit']), site='rssm.unif')
 
     # ---- single steps (API parity; acting / data-free paths)
-    def _prior_logits(self, deter):
+    def _prior_raw(self, deter):
         x = _dense_ln_silu(deter, self._ensemble_img_out[0][0], self._ensemble_img_out[0][1])
-        lg = ops.linear(x, self._ensemble_img_dist[0].weight, self._ensemble_img_dist[0].bias)
+        return ops.linear(x, self._ensemble_img_dist[0].weight, self._ensemble_img_dist[0].bias)
+
+    def _prior_logits(self, deter):
+        lg = self._prior_raw(deter)
         return lg.reshape(list(lg.shape[:-1]) + [self._stoch, self._discrete])
 
-    def _post_logits(self, embed, deter=None):
+    def _post_raw(self, embed, deter=None):
         if self.single_obs_posterior:
             x = _dense_ln_silu(embed, self._obs_out[0], self._obs_out[1])
         else:
             x = _dense_ln_silu(deter, self._obs_out[0], self._obs_out[1], embed)
-        lg = ops.linear(x, self._obs_dist.weight, self._obs_dist.bias)
+        return ops.linear(x, self._obs_dist.weight, self._obs_dist.bias)
+
+    def _post_logits(self, embed, deter=None):
+        lg = self._post_raw(embed, deter)
         return lg.reshape(list(lg.shape[:-1]) + [self._stoch, self._discrete])
 
-    def get_stoch_stats_from_deter_state(self, temp_state, sample=True, site='rssm.prior'):
+    def _gauss_stats(self, raw, sample, site, eps=None):
+        """_suff_stats_layer + get_dist(stats).sample() of the continuous branch (ref :513-521, :416-419) on a head's raw output
+        (..., 2S): -> stoch, {'mean', 'std'}.  sample False: stoch = mean -- what the reference's prior falls back to (ref :483-486);
+        its posterior calls `dist.mode()` without that guard (ref :456) and raises there, see DESIGN 5g.  eps: this step's slice of a
+        scan's noise, else drawn at `site`."""
+        if sample and eps is None:
+            eps = noise.draw('normal', site, tuple(raw.shape[:-1]) + (self._stoch,), raw.device)
+        mean, std, stoch = ops.gauss_head(raw, eps if sample else None, self._std_act, self._min_std)
+        return stoch, {'mean': mean, 'std': std}
+
+    def get_stoch_stats_from_deter_state(self, temp_state, sample=True, site='rssm.prior', eps=None):
+        if not self._discrete:
+            return self._gauss_stats(self._prior_raw(temp_state['deter']), bool(sample), site, eps)
         logit = self._prior_logits(temp_state['deter'])
         d = OneHotDist(logit, site=site)
         return (d.sample() if sample else d.mode()), {'logit': logit}
 
-    def img_step(self, prev_state, prev_action, sample=True, site='rssm.prior'):
+    def img_step(self, prev_state, prev_action, sample=True, site='rssm.prior', eps=None):
         x = _dense_ln_silu(self.get_stoch(prev_state), self._img_in[0], self._img_in[1], prev_action)
         deter = ops.gru_step(x, prev_state['deter'], self._cell._layer.weight, self._cell._norm.weight,
                              self._cell._norm.bias)
-        stoch, stats = self.get_stoch_stats_from_deter_state({'deter': deter}, bool(sample), site)
+        # (eps: continuous latents inside a scan hand in the step's slice of the scan's noise)
+        stoch, stats = self.get_stoch_stats_from_deter_state({'deter': deter}, bool(sample), site, eps)
         return {'stoch': stoch, 'deter': deter, **stats}
 
-    def get_post_stoch(self, embed, prior, should_sample=True):
+    def get_post_stoch(self, embed, prior, should_sample=True, eps=None):
+        if not self._discrete:
+            return self._gauss_stats(self._post_raw(embed, prior['deter']), bool(should_sample), 'rssm.post', eps)
         logit = self._post_logits(embed, prior['deter'])
         d = OneHotDist(logit, site='rssm.post')
         return (d.sample() if should_sample else d.mode()), {'logit': logit}
 
-    def obs_step(self, prev_state, prev_action, embed, is_first, should_sample=True):
+    def obs_step(self, prev_state, prev_action, embed, is_first, should_sample=True, eps=None):
+        """eps: (prior, posterior) N(0, 1) noise of this step when a scan over continuous latents drew it for all steps at once"""
         m = 1.0 - is_first.float()
         prev_state = {k: torch.einsum('b,b...->b...', m, v) for k, v in prev_state.items()}
         prev_action = torch.einsum('b,b...->b...', m, prev_action)
-        prior = self.img_step(prev_state, prev_action, should_sample)
-        stoch, stats = self.get_post_stoch(embed, prior, should_sample)
+        e_prior, e_post = eps if eps is not None else (None, None)
+        prior = self.img_step(prev_state, prev_action, should_sample, eps=e_prior)
+        stoch, stats = self.get_post_stoch(embed, prior, should_sample, e_post)
         return {'stoch': stoch, 'deter': prior['deter'], **stats}, prior
 
     # ---- sequences
@@ -609,6 +672,8 @@ class EnsembleRSSM(Module):  # ref :302-555
         projection and the prior head are batched over all T steps; only h_{t-1} W_h + LN + gates is
         sequential (ops.gru_seq).  Without it, falls back to the step-by-step form."""
         B, T = action.shape[:2]
+        if not self._discrete:       # (continuous latents: the batched form and the C scan are built around the categorical sample)
+            return self._observe_stepwise(embed, action, is_first, state)
         if not self.single_obs_posterior:
             # (the scan's C launch loop has the LayerNorm launches of `norm: layer` built in: norm-free layers go step by step)
             if self._norm == 'none' or os.environ.get('GENRL_OBSERVE_SEQ', '1') == '0':
@@ -673,8 +738,12 @@ class EnsembleRSSM(Module):  # ref :302-555
         B, T = action.shape[:2]
         state = state if state is not None else self.initial(B)
         posts, priors = [], []
+        if not self._discrete:       # one draw per site for the whole scan (T, B, S); a step consumes its slice
+            e_prior = _scan_noise('wm.prior_eps', 'rssm.prior', T, B, self._stoch, embed.device, 'normal')
+            e_post = _scan_noise('wm.post_eps', 'rssm.post', T, B, self._stoch, embed.device, 'normal')
         for t in range(T):
-            post, prior = self.obs_step(state, action[:, t], embed[:, t], is_first[:, t])
+            eps = (e_prior[t], e_post[t]) if not self._discrete else None
+            post, prior = self.obs_step(state, action[:, t], embed[:, t], is_first[:, t], eps=eps)
             posts.append(post); priors.append(prior); state = post
         st = lambda L: {k: torch.stack([d[k] for d in L], 1) for k in L[0]}
         return st(posts), st(priors)
@@ -683,6 +752,13 @@ class EnsembleRSSM(Module):  # ref :302-555
         """ref :373-381: prior rollout for given actions (B,T,A)."""
         B, T = action.shape[:2]
         state = state if state is not None else self.initial(B)
+        if not self._discrete:
+            eps = _scan_noise('rssm.imagine_eps', 'rssm.prior', T, B, self._stoch, action.device, 'normal') if sample else None
+            outs = []
+            for t in range(T):
+                state = self.img_step(state, action[:, t], sample, eps=eps[t] if sample else None)
+                outs.append(state)
+            return {k: torch.stack([d[k] for d in outs], 1) for k in outs[0]}
         if (not torch.is_grad_enabled() and action.is_cuda and self._norm != 'none'
                 and os.environ.get('GENRL_OBSERVE_SEQ', '1') != '0'):
             # forward only (the data-free block's warm-up rollouts, report, video_imagine all run under no_grad): the action half of
@@ -710,6 +786,8 @@ class EnsembleRSSM(Module):  # ref :302-555
         assert balance != 0.5 and not free_avg
         lhs, rhs = (prior, post) if forward else (post, prior)
         mix = balance if forward else (1 - balance)
+        if not self._discrete:       # the same node on Normal latents (torch's kl_normal_normal under Independent(., 1))
+            return ops.gauss_kl_balance(lhs['mean'], lhs['std'], rhs['mean'], rhs['std'], mix, free)
         l, r = lhs['logit'], rhs['logit']
         # mix * max(KL(l || sg r), free).mean() + (1 - mix) * max(KL(sg l || r), free).mean() as one autograd node
         return ops.kl_balance(l, r, mix, free)

@@ -37,6 +37,10 @@ def _chunk_embeddings(clip, n_frames, first, B, T):
 
 class GenRLAgent(DreamerAgent):
     def __init__(self, **kwargs):  # agent/genrl.py:28-49
+        cfg = kwargs['cfg']
+        if not cfg.rssm.get('discrete', False) or not cfg.connector_rssm.get('discrete', False):
+            raise NotImplementedError('GenRLAgent needs discrete latents (`rssm.discrete`, `connector_rssm.discrete`): its connector '
+                                      'teacher-forces one-hot latents; continuous latents are built for DreamerAgent and Plan2Explore')
         super().__init__(**kwargs)
         self.n_frames = N_FRAMES
         assert self.cfg.batch_length % self.n_frames == 0, 'Fix batch length param'

@@ -112,7 +112,8 @@ def dreamer_v2_settings():
 def dreamer_cfg(batch_size=64, batch_length=50, device='cuda', task='walker_walk', defaults='dreamer_v3', **over):
     """conf/defaults/dreamer_v3.yaml (defaults='dreamer_v2': dreamer_v2.yaml, see dreamer_v2_settings) + conf/env/dmc_pixels.yaml +
     agent/dreamer.yaml (BASELINE configs[2]: DreamerAgent, walker A=6).  Overrides `discrete_actions=True` (one-hot actor head) and, with it,
-    `actor_grad='reinforce'` select the discrete-action routes; both are passed through as given."""
+    `actor_grad='reinforce'` select the discrete-action routes; both are passed through as given.  An `rssm` override with
+    `discrete=False` (and `stoch`, `std_act` in softplus / sigmoid / sigmoid2, `min_std`) selects continuous latents."""
     assert defaults in ('dreamer_v3', 'dreamer_v2'), defaults
     rssm = dict(ensemble=1, hidden=512, deter=512, stoch=32, discrete=32, norm='layer', std_act='softplus', min_std=0.1,
                 single_obs_posterior=False)

@@ -2533,3 +2533,124 @@ def sqerr_like(out, x):
     """MSEDist(out).log_prob(x) of a one-wide head: out, x (..., 1) -> -(out - x)^2 of shape (...)"""
     assert out.shape[-1] == 1 and out.numel() == x.numel(), (out.shape, x.shape)
     return _SqErr.apply(out, x.detach().reshape(out.shape)).squeeze(-1)
+
+
+# ------------------------------------------------------------------ continuous (Gaussian) RSSM latents (csrc/gaussian.hip)
+
+STD_ACTS = {'softplus': 0, 'sigmoid': 1, 'sigmoid2': 2}
+
+
+def _rows_pitch(t2d):
+    """Rows of a 2-D operand for the Gaussian head without a copy: (tensor, row pitch).  A column slice of a wider buffer (the padded rows
+    ops.linear hands out) is read in place whatever its alignment: the head kernels pick their access width themselves."""
+    if t2d.stride(1) == 1 and t2d.stride(0) >= t2d.shape[1]:
+        return t2d, t2d.stride(0)
+    t2d = t2d.contiguous()
+    return t2d, t2d.shape[1]
+
+
+class _GaussHead(Function):
+    """EnsembleRSSM._suff_stats_layer with `discrete: False` (agent/dreamer_utils.py:513-521) and the reparameterised sample of get_dist
+    (:416-419) as one node: raw (..., 2S) -> mean, std = act(raw[..., S:]) + min_std, stoch = mean + std eps (eps None: stoch = mean)."""
+    @staticmethod
+    def forward(ctx, raw, eps, act, min_std):
+        ctx.set_materialize_grads(False)
+        S = raw.shape[-1] // 2
+        assert raw.shape[-1] == 2 * S and S > 0, raw.shape
+        _on_gpu(raw)
+        r2, ldr = _rows_pitch(_f32(raw).reshape(-1, 2 * S))
+        R = r2.shape[0]
+        e = _f32(eps.detach()).reshape(R, S).contiguous() if eps is not None else None
+        mean, std, stoch = (torch.empty(R, S, device=raw.device) for _ in range(3))
+        check(lib().genrl_gauss_head_fwd(_prows(r2), ldr, _p(e), _p(mean), _p(std), _p(stoch), R, S, act, min_std, _stream()),
+              'gauss_head_fwd')
+        ctx.save_for_backward(r2, e)
+        ctx.cfg = (act, ldr, raw.shape)
+        lead = tuple(raw.shape[:-1]) + (S,)
+        return mean.reshape(lead), std.reshape(lead), stoch.reshape(lead)
+
+    @staticmethod
+    def backward(ctx, dmean, dstd, dstoch):
+        r2, e = ctx.saved_tensors
+        act, ldr, rshape = ctx.cfg
+        if dmean is None and dstd is None and dstoch is None:
+            return None, None, None, None
+        R, S = r2.shape[0], r2.shape[1] // 2
+        # (contiguous copies of the upstream gradients stay referenced until the launch is enqueued)
+        gs, gm, gd = (_f32(t).reshape(R, S).contiguous() if t is not None else None for t in (dstoch, dmean, dstd))
+        d = torch.empty(R, 2 * S, device=r2.device)
+        check(lib().genrl_gauss_head_bwd(_p(gs), _p(gm), _p(gd), _prows(r2), ldr, _p(e), _p(d), 2 * S, R, S, act, 0, _stream()),
+              'gauss_head_bwd')
+        return d.reshape(rshape), None, None, None
+
+
+def gauss_head(raw, eps, std_act='softplus', min_std=0.1):
+    """raw (..., 2S) = [mean | std_raw] -> (mean, std, stoch), each (..., S); eps (..., S) N(0, 1) noise, None: the mean form (stoch = mean)"""
+    return _GaussHead.apply(raw, eps, STD_ACTS[std_act], float(min_std))
+
+
+def _same_order(ts):
+    """_time_major for operands that one kernel walks together: all in storage order when they share it, else all copied"""
+    got = [_time_major(_f32(t)) for t in ts]
+    if all(tm for _, tm in got) or not any(tm for _, tm in got):
+        return [t for t, _ in got], got[0][1]
+    return [(t.transpose(0, 1).contiguous() if tm else t) for t, tm in got], False
+
+
+class _GaussKLBalance(Function):
+    """_KLBalance for Normal latents: the Normal-Normal KL kernel, then genrl_kl_balance_fwd; backward: genrl_kl_balance_bwd's two per-row
+    vectors and ONE genrl_gauss_kl_bwd launch (gp scales the left side's gradients, gq the right side's)."""
+    @staticmethod
+    def forward(ctx, lm, ls, rm, rs, mix, free):
+        ctx.set_materialize_grads(False)
+        (lm, ls, rm, rs), tm = _same_order([lm, ls, rm, rs])
+        assert lm.shape == ls.shape == rm.shape == rs.shape, (lm.shape, ls.shape, rm.shape, rs.shape)
+        ctx.tm = tm
+        S = lm.shape[-1]
+        R = lm.numel() // S
+        kl = torch.empty(R, device=lm.device)
+        check(lib().genrl_gauss_kl_fwd(_p(lm), _p(ls), _p(rm), _p(rs), _p(kl), None, None, R, S, _stream()), 'gauss_kl_fwd')
+        loss = torch.empty((), device=lm.device)
+        check(lib().genrl_kl_balance_fwd(_p(kl), R, mix, free, _p(loss), _stream()), 'kl_balance_fwd')
+        ctx.save_for_backward(lm, ls, rm, rs, kl)
+        ctx.mix, ctx.free = mix, free
+        value = kl.reshape(lm.shape[:-1])
+        if tm:
+            value = value.transpose(0, 1)
+        ctx.mark_non_differentiable(value)
+        return loss, value
+
+    @staticmethod
+    def backward(ctx, gloss, _gvalue):
+        lm, ls, rm, rs, kl = ctx.saved_tensors
+        if gloss is None:
+            return None, None, None, None, None, None
+        S = lm.shape[-1]
+        R = kl.numel()
+        gp = torch.empty(R, device=lm.device); gq = torch.empty(R, device=lm.device)
+        check(lib().genrl_kl_balance_bwd(_p(kl), _p(gloss.contiguous()), R, ctx.mix, ctx.free, _p(gp), _p(gq), _stream()),
+              'kl_balance_bwd')
+        need = ctx.needs_input_grad
+        outs = [torch.empty_like(t) if need[i] else None for i, t in enumerate((lm, ls, rm, rs))]
+        if any(o is not None for o in outs):
+            check(lib().genrl_gauss_kl_bwd(_p(lm), _p(ls), _p(rm), _p(rs), _p(gp), _p(gq), _p(outs[0]), _p(outs[1]), _p(outs[2]),
+                                           _p(outs[3]), R, S, _stream()), 'gauss_kl_bwd')
+        if ctx.tm:
+            outs = [o.transpose(0, 1) if o is not None else None for o in outs]
+        return outs[0], outs[1], outs[2], outs[3], None, None
+
+
+def gauss_kl_balance(lhs_mean, lhs_std, rhs_mean, rhs_std, mix, free):
+    """EnsembleRSSM.kl_loss on Normal latents (balance != 0.5, free_avg False) -> (scalar loss, per-row KL value [detached])"""
+    return _GaussKLBalance.apply(lhs_mean, lhs_std, rhs_mean, rhs_std, float(mix), float(free))
+
+
+def gauss_entropy(std):
+    """Independent(Normal(., std), 1).entropy(): sum over the last dimension of 0.5 + 0.5 log 2 pi + log std (a metric: no gradient)"""
+    sd, tm = _time_major(_f32(std.detach()))
+    S = sd.shape[-1]
+    R = sd.numel() // S
+    ent = torch.empty(R, device=sd.device)
+    check(lib().genrl_gauss_kl_fwd(None, _p(sd), None, None, None, _p(ent), None, R, S, _stream()), 'gauss_kl_fwd')
+    ent = ent.reshape(sd.shape[:-1])
+    return ent.transpose(0, 1) if tm else ent

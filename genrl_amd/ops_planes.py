@@ -629,10 +629,11 @@ def imagine_rollout(stoch0, deter0, logit0, eps, q, spec):
 
 
 # ---- the Plan2Explore ensemble (agent/plan2explore.py:8-41): members of Linear([obs, action]) -> ReLU -> Linear
-def _member_route(M):
+def _member_route(M, D=0):
     """plane operands for the member products?  (as everywhere: from min_rows() rows up while the plane path is on -- a precision-16
-    agent has switched it off, and the fp32-operand kernels then round to bf16 themselves)"""
-    return pl.ENABLED and M >= min_rows()
+    agent has switched it off, and the fp32-operand kernels then round to bf16 themselves; an observation width D that is no multiple of 4
+    -- continuous latents with `stoch: 30` -- stays on the fp32-operand kernels, whose scalar-load form takes any width)"""
+    return pl.ENABLED and M >= min_rows() and D % 4 == 0
 
 
 class EnsembleInputs:
@@ -645,7 +646,7 @@ class EnsembleInputs:
         self.M, self.D = self.obs.shape
         self.A = self.act.shape[1]
         assert self.act.shape[0] == self.M
-        self.on_planes = _member_route(self.M) if on_planes is None else on_planes
+        self.on_planes = _member_route(self.M, self.D) if on_planes is None else on_planes
         self.Po = pl.split(self.obs.detach()) if self.on_planes else None
         self.Pa = pl.split(self.act) if self.on_planes else None
 
@@ -791,7 +792,7 @@ class _Disagreement(Function):
         need_j = ctx.needs_input_grad[0]
         r = torch.empty(M, device=dev)
         J = torch.empty(M, D, device=dev) if need_j else None
-        on_planes = _member_route(M)
+        on_planes = _member_route(M, D)
         C = disagreement_chunk_rows()
         E = params[2].shape[0]
         for c0 in range(0, M, C):

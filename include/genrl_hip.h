@@ -663,6 +663,30 @@ int genrl_reinforce_obj_bwd(const float* g, const float* target, const float* ba
                             const float* offset_scale, float ent_scale, int H, long N, float* dlogp, float* dtarget,
                             float* dbaseline, float* dent, void* stream);
 
+/* ---- continuous (Gaussian) RSSM latents (`rssm.discrete: False`, agent/dreamer_utils.py:333-335, :416-419, :513-521; genrl_amd/csrc/gaussian.hip)
+ * std_act: 0 softplus (torch's: x above the threshold 20, log1p(exp(x)) below), 1 sigmoid, 2 sigmoid2 = 2 sigmoid(x / 2).  Every entry
+ * returns 1 before any launch for S < 1, a pitch below 2 S, an unknown std_act, a missing required pointer or no output at all.
+ * genrl_gauss_head_fwd: raw [R, 2S] with row pitch ldr = [mean | std_raw]: mean = raw[:, :S], std = act(raw[:, S:]) + min_std,
+ *   stoch = mean + std eps (eps [R, S]; NULL: the mean form, stoch = mean).  mean, std, stoch are [R, S], contiguous; any of them may be
+ *   NULL.  No alignment is required of raw, S or ldr: 16-byte accesses are used when every pointer, S and ldr allow them.
+ * genrl_gauss_head_bwd: draw [R, 2S] with row pitch lddr: draw[:, :S] = dstoch + dmean, draw[:, S:] = (dstoch eps + dstd) act'(raw[:, S:]);
+ *   each of dstoch, dmean, dstd [R, S] may be NULL (zero; at least one is given), eps NULL: the mean form.  accumulate != 0 adds into
+ *   draw.  Columns of draw past 2S are not written.
+ * genrl_gauss_kl_fwd: kl[m] = sum_s 0.5 (v + t - 1 - log v), v = (std_l / std_r)^2, t = ((mean_l - mean_r) / std_r)^2 (torch's
+ *   kl_normal_normal summed by Independent(., 1)); ent_x[m] = sum_s (0.5 + 0.5 log 2 pi + log std_x).  Inputs [R, S] contiguous, any S >= 1;
+ *   kl, ent_l, ent_r may be NULL (not all); without kl only the std of the requested entropies is read.  Sums are accumulated in double
+ *   in a fixed order.
+ * genrl_gauss_kl_bwd: elementwise; gp[m] scales the gradient into (mean_l, std_l), gq[m] into (mean_r, std_r) -- the two per-row vectors
+ *   of genrl_kl_balance_bwd.  Any of the four outputs may be NULL (not all); gp / gq is read only for a side with an output. */
+int genrl_gauss_head_fwd(const float* raw, long ldr, const float* eps, float* mean, float* std, float* stoch, long R, int S,
+                         int std_act, float min_std, void* stream);
+int genrl_gauss_head_bwd(const float* dstoch, const float* dmean, const float* dstd, const float* raw, long ldr, const float* eps,
+                         float* draw, long lddr, long R, int S, int std_act, int accumulate, void* stream);
+int genrl_gauss_kl_fwd(const float* mean_l, const float* std_l, const float* mean_r, const float* std_r, float* kl, float* ent_l,
+                       float* ent_r, long R, int S, void* stream);
+int genrl_gauss_kl_bwd(const float* mean_l, const float* std_l, const float* mean_r, const float* std_r, const float* gp,
+                       const float* gq, float* dmean_l, float* dstd_l, float* dmean_r, float* dstd_r, long R, int S, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
