@@ -77,7 +77,6 @@ class DreamerAgent(Module):
         # precision 16 is ONE arithmetic -- every matrix product rounds both operands to bf16 and accumulates in fp32 (what
         # oracle/genrl_oracle.py restates as `bf16_operands`, tests/test_gpu_iteration.py::test_precision16_vs_the_oracles_bf16_operand_mode) -- so the pre-split fp16-plane
         # products (fp32-grade) are switched off while an agent of that precision runs, and back on for the next fp32 agent
-        from .. import planes
         if self._use_amp:
             if planes._amp_saved is None:
                 planes._amp_saved = planes.ENABLED
@@ -135,17 +134,6 @@ class DreamerAgent(Module):
 
     def update_meta(self, meta, global_step, time_step, finetune=False):
         return meta
-
-
-_constants = {}
-
-
-def _constant(shape, value, dev):
-    """read-only constant tensor, cached per (shape, value, device)"""
-    key = (tuple(shape), float(value), str(dev))
-    if key not in _constants:
-        _constants[key] = torch.full(tuple(shape), float(value), device=dev)
-    return _constants[key]
 
 
 def _flat_stoch(stoch, deter):
@@ -331,53 +319,24 @@ class WorldModel(Module):  # ref :120-321
         N = start['deter'].shape[0]
         dev = start['deter'].device
         A = policy._out._out.out_features
-        # the policy's head by its distribution: DistLayer 'normal' (dreamer_v3 / genrl defaults), 'trunc_normal' (dreamer_v2) or 'onehot'
-        # (`discrete_actions`; its draws are exponential-race noise from a site of their own)
-        onehot = policy._out._dist == 'onehot'
-        if onehot:
-            eps = noise.draw('exp', 'imag.act_q', (horizon, N, A), dev) if not eval_policy else None
-        else:
-            eps = noise.draw('normal', 'imag.act_eps', (horizon, N, A), dev) if not eval_policy else None
-        rssm = self.rssm
-        gauss = not rssm._discrete          # continuous latents: N(0, 1) noise for the reparameterised samples, one slice per step
-        if gauss:
-            step_eps = noise.draw('normal', 'imag.step_eps', (horizon, N, rssm._stoch), dev)
-        else:
-            q = noise.draw('exp', 'imag.step_q', (horizon, N * self.rssm._stoch, self.rssm._discrete), dev)
+        rssm, head, lat = self.rssm, policy._out._head, self.rssm._latent      # (the policy's head and the latent by their kinds)
+        eps = noise.draw(*head.noise, (horizon, N, A), dev) if not eval_policy else None
+        step_noise = noise.draw(lat.noise_kind, f'imag.step_{lat.noise_suffix}', (horizon,) + lat.noise_shape((N,)), dev)
         seq = {k: [v] for k, v in start.items()}
         seq['action'] = [torch.zeros(N, A, device=dev)]
-        trunc = policy._out._dist == 'trunc_normal'
-        if onehot:          # eval_policy: the mixed probabilities (OneHotDist.mean, ref :266); the reference's throw-away sample (ref :259-260) stays dropped
-            head_mean = ops.onehot_probs
-            head_sample = ops.onehot_sample
-        elif trunc:
-            head_mean = lambda raw: ops.trunc_normal_mean_std(raw, policy._out._min_std, policy._out._init_std)[0]
-            head_sample = lambda raw, e: ops.trunc_normal_sample(raw, e, policy._out._min_std, policy._out._init_std)
-        else:
-            assert policy._out._dist == 'normal', policy._out._dist
-            head_mean = lambda raw: ops.actor_mean_std(raw, policy._out._min_std, policy._out._max_std)[0]
-            head_sample = lambda raw, e: ops.actor_sample(raw, e, policy._out._min_std, policy._out._max_std)
-        # the two heads of DistLayer('normal' / 'trunc_normal') (mean, std) as ONE product: weights stacked once per rollout
-        if onehot:
-            head_w, head_b = policy._out._out.weight, policy._out._out.bias
-        else:
-            head_w = torch.cat([policy._out._out.weight, policy._out._std.weight], 0)
-            head_b = torch.cat([policy._out._out.bias, policy._out._std.bias], 0)
+        head_w, head_b = head.weights()         # (mean and std heads as ONE product: weights stacked once per rollout)
         raws = []
-        # training rollouts: the policy's H backward passes are batched into one over all H*N rows
-        # (the tape, the fused rollout and their C launch loops have the LayerNorm launches and the Normal head built in: a norm-free
-        # world model or policy, or a truncated-normal or one-hot head, takes the step-by-step loop below; so do continuous latents, which
-        # the tape's state planes and the fused rollout's categorical sample know nothing of)
-        tape = None
+        # training rollouts: the policy's H backward passes are batched into one over all H*N rows (the tape, the fused rollout and their C
+        # launch loops have the LayerNorm launches, the Normal head and the categorical sample built in: the rest goes step by step below)
+        tape = state_planes = None
         if (torch.is_grad_enabled() and head_w.requires_grad and horizon > 1 and policy._norm != 'none' and rssm._norm != 'none'
-                and not trunc and not onehot and not gauss):
+                and head.fused and lat.fused):
             layers = [(getattr(policy, f'dense{i}').weight, getattr(policy, f'dense{i}').bias,
                        getattr(policy, f'norm{i}')._layer.weight, getattr(policy, f'norm{i}')._layer.bias,
                        getattr(policy, f'norm{i}')._layer.eps) for i in range(policy._layers)]
             # (plane operands pay from ~512 rollout rows up: below, every product is launch-latency bound either way and
             # the plane writes only add traffic -- measured 14.2 vs 13.7 ms/step at 4 sequences per GPU)
-            use_planes = planes.ENABLED and N >= ops_planes.min_rows()
-            tape = (ops_planes.ActorTapePlanes if use_planes else ops.ActorTape)(horizon, N, layers, head_w, head_b, dev)
+            tape = (ops_planes.ActorTapePlanes if common.planes_route(N) else ops.ActorTape)(horizon, N, layers, head_w, head_b, dev)
             tape.head_leaves = (policy._out._out.weight, policy._out._out.bias, policy._out._std.weight, policy._out._std.bias)
         fused = tape is not None and not eval_policy and set(start) == {'stoch', 'deter', 'logit'}
         if fused:
@@ -388,44 +347,38 @@ class WorldModel(Module):  # ref :120-321
             spec = ops.RolloutSpec(tape, inl.weight, inl.bias, inn.weight, inn.bias, inn.eps,
                                    rssm._cell._layer.weight, rssm._cell._norm.weight, rssm._cell._norm.bias,
                                    outl.weight, outl.bias, outn.weight, outn.bias, outn.eps, dist.weight, dist.bias,
-                                   rssm._stoch, rssm._discrete, policy._out._min_std, policy._out._max_std)
+                                   *lat.shape, policy._out._min_std, policy._out._max_std)
             roll = ops_planes.imagine_rollout if isinstance(tape, ops_planes.ActorTapePlanes) else ops.imagine_rollout
-            st, de, lg, ac, raw_all = roll(start['stoch'], start['deter'], start['logit'], eps, q, spec)
+            st, de, lg, ac, raw_all = roll(start['stoch'], start['deter'], start['logit'], eps, step_noise, spec)
             seq = {'stoch': st, 'deter': de, 'logit': lg, 'action': ac}
             self._last_actor_raw = raw_all
             state_planes = getattr(tape, 'state_planes', None)
         else:
             for h in range(horizon):
-                stoch, deter = seq['stoch'][-1], seq['deter'][-1]
-                s_flat = stoch.reshape(N, -1)
+                state = {'stoch': seq['stoch'][-1], 'deter': seq['deter'][-1]}
+                s_flat, deter = rssm.get_stoch(state), state['deter']
                 if tape is not None:
                     raw = tape.step(h, stop_gradient(s_flat), stop_gradient(deter))
                 else:
                     raw = ops.linear(policy.trunk(stop_gradient(s_flat), stop_gradient(deter)), head_w, head_b)
                 raws.append(raw)
-                action = head_mean(raw) if eval_policy else head_sample(raw, eps[h])
-                x = common._dense_ln_silu(s_flat, rssm._img_in[0], rssm._img_in[1], action)
-                deter = ops.gru_step(x, deter, rssm._cell._layer.weight, rssm._cell._norm.weight, rssm._cell._norm.bias)
-                if gauss:       # (whatever keys the state has are carried: mean and std beside stoch and deter)
-                    stoch, stats = rssm._gauss_stats(rssm._prior_raw(deter), True, 'imag.step_eps', step_eps[h])
-                else:
-                    logit = rssm._prior_logits(deter)
-                    stoch, stats = ops.onehot_sample(logit, q[h]), {'logit': logit}
-                for key, value in dict(stoch=stoch, deter=deter, action=action, **stats).items():
-                    seq[key].append(value)
+                # eval_policy: the head's mean (ref :266); the reference's throw-away sample (ref :259-260) stays dropped
+                action = head.mean(raw) if eval_policy else head.sample(raw, eps[h])
+                for key, value in dict(rssm.img_step(state, action, eps=step_noise[h]), action=action).items():
+                    seq[key].append(value)          # (whatever keys the step's state has: logit, or mean and std, beside stoch and deter)
             seq = {k: torch.stack(v, 0) for k, v in seq.items()}
             if tape is not None:     # layer-0 inputs of all steps = the stacked rollout states (no copies)
                 tape.inputs = (seq['stoch'].detach().reshape(horizon + 1, N, -1), seq['deter'].detach())
-            # policy outputs at states 0..H-1 — exactly what ActorCritic.actor_loss re-evaluates for its
-            # entropy metric (agent/dreamer.py:397: actor(sg(feat[:-2]))): kept to avoid a second forward
-            self._last_actor_raw = torch.stack(raws, 0)          # (H, N, 2A) -- one-hot head: the logits (H, N, A) --, attached to the actor's graph
+            # policy outputs at states 0..H-1 -- what ActorCritic.actor_loss re-evaluates for its entropy (agent/dreamer.py:397:
+            # actor(sg(feat[:-2]))): kept to avoid a second forward.  (H, N, head.raw width), attached to the actor's graph
+            self._last_actor_raw = torch.stack(raws, 0)
         seq = _ImaginedSeq(rssm, seq)                  # 'feat' = cat(stoch, deter) (ref :272) on first access
-        seq.planes = locals().get('state_planes')          # (planes of stoch / deter, rows h*N + n, from the fused rollout)
+        seq.planes = state_planes          # (planes of stoch / deter, rows h*N + n, from the fused rollout)
         # no discount head (conf/env/dmc_pixels.yaml:6): discount = gamma everywhere and weight = cumprod(ones) = 1
         # (ref :274-286) -- constants, built once per shape instead of five launches per update
         shape = tuple(seq['deter'].shape[:-1]) + (1,)
-        seq['discount'] = _constant(shape, float(self.cfg.discount), dev)
-        seq['weight'] = _constant(shape, 1.0, dev)
+        seq['discount'] = common._const(shape, float(self.cfg.discount), dev)
+        seq['weight'] = common._const(shape, 1.0, dev)
         seq.unit_weight = True
         return seq
 
@@ -464,9 +417,9 @@ class ActorCritic(Module):  # ref :323-462
         self.actor_grad = getattr(self.cfg, f'{self.name}_actor_grad'.strip('_'))
         if self.actor_grad not in ('dynamics', 'reinforce'):      # ref :413-419
             raise NotImplementedError(self.actor_grad)
-        if self.actor_grad == 'reinforce' and self.cfg.actor.dist != 'onehot':
-            raise NotImplementedError('actor_grad reinforce is implemented for the one-hot head of discrete_actions')
         self.actor = common.MLP(feat_size, act_spec.shape[0], **self.cfg.actor)
+        if self.actor_grad == 'reinforce' and not self.actor._out._head.reinforce:
+            raise NotImplementedError('actor_grad reinforce is implemented for the one-hot head of discrete_actions')
         self.critic = common.MLP(feat_size, (1,), **self.cfg.critic)
         assert self.cfg.slow_target
         self._target_critic = common.MLP(feat_size, (1,), **self.cfg.critic)
@@ -596,36 +549,15 @@ class ActorCritic(Module):  # ref :323-462
             metrics['reward_ema_005'] = self.ema_vals[0].clone()
             metrics['reward_ema_095'] = self.ema_vals[1].clone()
             objective = normed_target[1:]
-        raw = self._policy_raw(seq)
-        A = raw.shape[-1] // 2
-        mn, mx = self.actor._out._min_std, self.actor._out._max_std
-        trunc = self.actor._out._dist == 'trunc_normal'
-        if self.actor._out._dist == 'onehot':       # `discrete_actions`: the entropy of the unimix categorical over the logits
-            with contextlib.nullcontext() if ent_scale != 0 else torch.no_grad():
-                ent = ops.onehot_logp_ent(raw, None)[1][:, :, None]
-            if ent_scale != 0:
-                objective = objective + ent_scale * ent
-                if not ema:         # (the in-place `objective += ent_scale * ent` on a view of the returns: see below)
-                    self._critic_target = torch.cat([target[:1], objective], 0).detach()
-            metrics['actor_ent'] = ops.wmean(ent.detach(), None, 1.0)
-        elif ent_scale != 0 or trunc:
-            # (the entropy of the untruncated Normal in both cases; with a truncated-normal head and scale 0 it is a metric only)
-            with contextlib.nullcontext() if ent_scale != 0 else torch.no_grad():
-                if trunc:           # ref dreamer_utils.py:832
-                    std = 2.0 * torch.sigmoid((raw[..., A:] + self.actor._out._init_std) / 2.0) + mn
-                else:
-                    std = (mx - mn) * torch.sigmoid(raw[..., A:] + 2.0) + mn
-                ent = (0.5 + 0.5 * np.log(2 * np.pi) + torch.log(std)).sum(-1)[:, :, None]
-            if ent_scale != 0:
-                objective = objective + ent_scale * ent
-                if not ema:
-                    # the reference's `objective += ent_scale * ent` (ref :423) works IN PLACE on `normed_target[1:]`, which without the
-                    # return EMA is a view of the lambda-returns themselves (ref :410, :414): the critic that follows regresses onto
-                    # returns that carry the entropy bonus from step 1 on.  Restated, not imitated: the returns stay untouched here
-                    self._critic_target = torch.cat([target[:1], objective], 0).detach()
-            metrics['actor_ent'] = ent.detach().mean()
-        else:                           # a metric only: no backward through it (its scale is 0); one launch
-            metrics['actor_ent'] = ops.normal_entropy_mean(raw, mn, mx)
+        raw, head, ent = self._policy_raw(seq), self.actor._out._head, None
+        if ent_scale != 0:
+            ent = head.entropy_grad(raw)
+            objective = objective + ent_scale * ent
+            if not ema:
+                # the reference's `objective += ent_scale * ent` (ref :423) works IN PLACE on a view of the lambda-returns (ref :410, :414):
+                # its critic regresses onto returns that carry the entropy bonus from step 1 on.  Restated, not imitated
+                self._critic_target = torch.cat([target[:1], objective], 0).detach()
+        metrics['actor_ent'] = head.entropy_mean(raw, ent)      # (scale 0: a metric only, no backward through it)
         metrics['actor_ent_scale'] = ent_scale
         if not ema:                     # -(weight[:-2] * objective).mean() as one node
             actor_loss = ops.wmean(objective, None if getattr(seq, 'unit_weight', False) else weight[:-2], -1.0)

@@ -177,47 +177,123 @@ class LatentNormalDist:
 
 
 class NormalDist:
-    """Independent(Normal(tanh(out), std), 1) of DistLayer 'normal' (ref :814-819)."""
-    def __init__(self, raw, min_std, max_std, site='actor'):
-        self.raw, self.min_std, self.max_std, self.site = raw, min_std, max_std, site
+    """Independent(Normal(tanh(out), std), 1) of DistLayer 'normal' (ref :814-819) or, by its head (HEADS below), 'trunc_normal':
+    Independent(TruncatedNormal(tanh(out), std), 1) (ref :830-834, tools/utils.py:102-123), whose sample is clamped to [-1 + 1e-6, 1 - 1e-6]
+    in value with the identity as its gradient and whose mean and entropy are the untruncated Normal's (pyd.Normal's, as the reference's)."""
+    def __init__(self, raw, head, site='actor'):
+        self.raw, self.head, self.site = raw, head, site
 
     def sample(self):
         A = self.raw.shape[-1] // 2
         eps = noise.draw('normal', self.site, tuple(self.raw.shape[:-1]) + (A,), self.raw.device)
-        return ops.actor_sample(self.raw, eps, self.min_std, self.max_std)
+        return self.head.sample(self.raw, eps)
 
     rsample = sample
 
     @property
     def mean(self):
-        return ops.actor_mean_std(self.raw, self.min_std, self.max_std)[0]
+        return self.head.mean(self.raw)
 
     def entropy(self):
-        std = ops.actor_mean_std(self.raw, self.min_std, self.max_std)[1]
-        return (0.5 + 0.5 * np.log(2 * np.pi) + torch.log(std)).sum(-1)
+        return (0.5 + 0.5 * np.log(2 * np.pi) + torch.log(self.head.mean_std(self.raw)[1])).sum(-1)
 
 
-class TruncNormalDist:
-    """Independent(TruncatedNormal(tanh(out), std), 1) of DistLayer 'trunc_normal' (ref :830-834, tools/utils.py:102-123):
-    std = 2 sigmoid((raw_std + init_std) / 2) + min_std; a sample is clamped to [-1 + 1e-6, 1 - 1e-6] in value with the identity as
-    its gradient; mean and entropy are the untruncated Normal's (pyd.Normal's, which the reference inherits)."""
-    def __init__(self, raw, min_std, init_std, site='actor'):
-        self.raw, self.min_std, self.init_std, self.site = raw, min_std, init_std, site
+TruncNormalDist = NormalDist
 
-    def sample(self):
-        A = self.raw.shape[-1] // 2
-        eps = noise.draw('normal', self.site, tuple(self.raw.shape[:-1]) + (A,), self.raw.device)
-        return ops.trunc_normal_sample(self.raw, eps, self.min_std, self.init_std)
 
-    rsample = sample
+# ----------------------------------------------------------------------------- policy / output heads
 
-    @property
-    def mean(self):
-        return ops.trunc_normal_mean_std(self.raw, self.min_std, self.init_std)[0]
+class _Head:
+    """What the code around a DistLayer asks about its `dist`: one subclass per kind, listed in HEADS.  A policy head (`noise` set) also
+    has sample(raw, noise), mean(raw) and the entropy from raw in the forms its callers use: entropy_grad (differentiable, (..., 1): what the
+    actor objective adds), entropy_mean (the metric, from entropy_grad's if given) and the kernels behind the distribution object's."""
+    has_std = False          # a second Linear `_std` beside `_out`: raw = [out | std_raw], twice as wide
+    planes_linear = False    # the head product may read the operand planes the trunk left (DistLayer.raw)
+    fused = False            # the policy tape and the fused rollout have this head built in (WorldModel.imagine)
+    reinforce = False        # actor_grad 'reinforce' is implemented on it
+    noise = None             # (kind, site) of a rollout's action noise
 
-    def entropy(self):
-        std = ops.trunc_normal_mean_std(self.raw, self.min_std, self.init_std)[1]
-        return (0.5 + 0.5 * np.log(2 * np.pi) + torch.log(std)).sum(-1)
+    def __init__(self, layer):
+        self.layer = layer
+
+    def weights(self):          # (weight, bias) of the head as ONE product: `_out` and `_std` stacked
+        L = self.layer
+        if not self.has_std:
+            return L._out.weight, L._out.bias
+        return torch.cat([L._out.weight, L._std.weight], 0), torch.cat([L._out.bias, L._std.bias], 0)
+
+    def entropy_mean(self, raw, ent=None):
+        if ent is None:         # a metric only: no backward through it
+            with torch.no_grad():
+                ent = self.entropy_grad(raw)
+        return self.reduce(ent.detach())
+
+    reduce = staticmethod(torch.mean)
+
+
+class _TwoHotHead(_Head):
+    planes_linear, dist = True, TwoHotDist
+
+
+class _MSEHead(_Head):
+    def dist(self, raw):
+        return MSEHeadDist(raw.reshape(list(raw.shape[:-1]) + list(self.layer._shape)))
+
+
+class _NormalHead(_Head):
+    """'normal': std = (max_std - min_std) sigmoid(raw_std + 2) + min_std, ops.actor_*.  trunc ('trunc_normal'): std = 2 sigmoid((raw_std +
+    init_std) / 2) + min_std (ref :832), ops.trunc_normal_*; the entropy is the untruncated Normal's and has no one-launch metric kernel."""
+    has_std, noise = True, ('normal', 'imag.act_eps')
+
+    def __init__(self, layer, trunc=False):
+        self.layer, self.trunc, self.fused = layer, trunc, not trunc
+
+    def params(self):
+        return self.layer._min_std, self.layer._init_std if self.trunc else self.layer._max_std
+
+    def sample(self, raw, eps):
+        return (ops.trunc_normal_sample if self.trunc else ops.actor_sample)(raw, eps, *self.params())
+
+    def mean_std(self, raw):         # (kernels, no gradient: NormalDist's mean and entropy)
+        return (ops.trunc_normal_mean_std if self.trunc else ops.actor_mean_std)(raw, *self.params())
+
+    def mean(self, raw):
+        return self.mean_std(raw)[0]
+
+    def entropy_grad(self, raw):
+        (mn, p), raw_std = self.params(), raw[..., raw.shape[-1] // 2:]
+        std = 2.0 * torch.sigmoid((raw_std + p) / 2.0) + mn if self.trunc else (p - mn) * torch.sigmoid(raw_std + 2.0) + mn
+        return (0.5 + 0.5 * np.log(2 * np.pi) + torch.log(std)).sum(-1)[..., None]
+
+    def entropy_mean(self, raw, ent=None):
+        if ent is None and not self.trunc:
+            return ops.normal_entropy_mean(raw, *self.params())       # (one launch)
+        return super().entropy_mean(raw, ent)
+
+    def dist(self, raw):
+        return NormalDist(raw, self)
+
+
+class _OneHotHead(_Head):
+    """`discrete_actions`: the logits of a unimix categorical; its draws are exponential-race noise from a site of their own"""
+    planes_linear, reinforce, noise = True, True, ('exp', 'imag.act_q')
+    reduce = staticmethod(lambda ent: ops.wmean(ent, None, 1.0))
+
+    def sample(self, raw, q):
+        return ops.onehot_sample(raw, q)
+
+    def mean(self, raw):             # the mixed probabilities (OneHotDist.mean, ref :266)
+        return ops.onehot_probs(raw)
+
+    def entropy_grad(self, raw):
+        return ops.onehot_logp_ent(raw, None)[1][..., None]
+
+    def dist(self, raw):
+        return OneHotDist(raw.float(), site='actor', independent=False)
+
+
+HEADS = {'mse': _MSEHead, 'twohot': _TwoHotHead, 'normal': _NormalHead, 'trunc_normal': lambda layer: _NormalHead(layer, trunc=True),
+         'onehot': _OneHotHead}
 
 
 # ----------------------------------------------------------------------------- scans (API parity)
@@ -258,25 +334,23 @@ def get_act(name):
     raise NotImplementedError(name)
 
 
-_zero_cache = {}
-_one_cache = {}
+_consts = {}
 
 
-def _one_like(t):
-    key = (tuple(t.shape), str(t.device), t.dtype)
-    if key not in _one_cache:
-        _one_cache[key] = torch.ones(tuple(t.shape), device=t.device, dtype=t.dtype)
-    return _one_cache[key]
+def _const(shape, value, dev, dtype=torch.float32):
+    """A constant tensor that is never written (initial RSSM states are replaced, not updated in place; a backward pass's seed): cached,
+    so that a training step does not spend a fill launch on it and a replayed graph finds it at the address it captured."""
+    key = (tuple(shape), float(value), str(dev), dtype)
+    if key not in _consts:
+        _consts[key] = torch.full(tuple(shape), float(value), device=dev, dtype=dtype)
+    return _consts[key]
 
 
-
-def _zeros(shape, dev):
-    """A zero tensor that is never written (initial RSSM states are replaced, not updated in place): cached per shape so
-    that a training step does not spend a fill launch per state entry."""
-    key = (tuple(shape), str(dev))
-    if key not in _zero_cache:
-        _zero_cache[key] = torch.zeros(tuple(shape), device=dev)
-    return _zero_cache[key]
+def planes_route(rows, switch=None, widths=(), cuda=True):
+    """Whether a product over `rows` rows takes the plane-operand kernels (ops_planes): planes enabled, on the GPU, from
+    ops_planes.min_rows() rows up, every width in `widths` a multiple of 4, and the environment switch `switch` (read per call) not '0'."""
+    return bool(pl.ENABLED and cuda and rows >= ops_planes.min_rows() and all(w % 4 == 0 for w in widths)
+                and (switch is None or os.environ.get(switch, '1') != '0'))
 
 
 class NormLayer(Module):  # ref :844-859
@@ -311,16 +385,13 @@ def _dense_ln_silu(x, lin, norm, x2=None, planes=None):
     the inputs (genrl_amd/planes.py) when the caller has them.  NormLayer('none') (conf/defaults/dreamer_v2.yaml): Linear without
     bias + SiLU (dense_act), under the same row threshold and switch.  A first input whose width is no multiple of 4 (continuous latents
     with the reference's `stoch: 30`) stays on the fp32-operand kernels, whose scalar-load form takes any width and row spacing."""
-    rows = x.numel() // x.shape[-1]
-    wide4 = x.shape[-1] % 4 == 0
+    use_planes = planes_route(x.numel() // x.shape[-1], 'GENRL_PLANES_MLP', (lin.weight.shape[0], x.shape[-1]), x.is_cuda)
     if norm._layer is None:
         assert lin.bias is None, 'a norm-free layer has no bias (ref :339-346, :734)'
-        if (pl.ENABLED and x.is_cuda and rows >= ops_planes.min_rows() and lin.weight.shape[0] % 4 == 0 and wide4
-                and os.environ.get('GENRL_PLANES_MLP', '1') != '0'):
+        if use_planes:
             return ops_planes.dense_act(x, x2, lin.weight, planes=planes)
         return ops.dense_act(x, x2, lin.weight)
-    if (pl.ENABLED and x.is_cuda and rows >= ops_planes.min_rows() and lin.weight.shape[0] % 4 == 0 and wide4
-            and os.environ.get('GENRL_PLANES_MLP', '1') != '0'):  # (-0.75 ms/step at c2 with the BK-64 128x128 tile, DESIGN 4a)
+    if use_planes:          # (-0.75 ms/step at c2 with the BK-64 128x128 tile, DESIGN 4a)
         return ops_planes.dense_ln_act(x, x2, lin.weight, lin.bias, norm._layer.weight, norm._layer.bias, norm._layer.eps,
                                    planes=planes)
     return ops.dense_ln_act(x, x2, lin.weight, lin.bias, norm._layer.weight, norm._layer.bias, norm._layer.eps)
@@ -337,7 +408,7 @@ class GRUCell(Module):  # ref :750-785
         self._norm = nn.LayerNorm(3 * size)
 
     def get_initial_state(self, inputs=None, batch_size=None, dtype=None):
-        return _zeros((batch_size, self._size), self.device)
+        return _const((batch_size, self._size), 0.0, self.device)
 
     @property
     def state_size(self):
@@ -355,36 +426,24 @@ class DistLayer(Module):  # ref :787-841
         self._shape = shape if type(shape) in [list, tuple] else [shape]
         self._dist, self._min_std, self._init_std, self._max_std = dist, min_std, init_std, max_std
         self._out = nn.Linear(in_dim, int(np.prod(shape)), bias=bias)
-        if dist in ('normal', 'trunc_normal'):
-            self._std = nn.Linear(in_dim, int(np.prod(shape)))
-        elif dist not in ('twohot', 'mse', 'onehot'):
+        if dist not in HEADS:
             raise NotImplementedError(dist)
+        self._head = HEADS[dist](self)
+        if self._head.has_std:
+            self._std = nn.Linear(in_dim, int(np.prod(shape)))
 
     def raw(self, inputs):
         h = getattr(inputs, '_planes', None)          # the trunk's last layer left its output's operand planes (ops_planes)
-        rows = inputs.numel() // inputs.shape[-1]
-        if (h is not None and pl.ENABLED and self._dist not in ('normal', 'trunc_normal', 'mse') and rows >= ops_planes.min_rows()
-                and os.environ.get('GENRL_PLANES_LINEAR', '1') != '0'):
+        if h is not None and self._head.planes_linear and planes_route(inputs.numel() // inputs.shape[-1], 'GENRL_PLANES_LINEAR'):
             return ops_planes.linear(inputs, self._out.weight, self._out.bias, h)
         out = ops.linear(inputs, self._out.weight, self._out.bias)
-        if self._dist in ('normal', 'trunc_normal'):
+        if self._head.has_std:
             std = ops.linear(inputs, self._std.weight, self._std.bias)
             return torch.cat([out, std], -1)
         return out
 
     def forward(self, inputs):
-        raw = self.raw(inputs)
-        if self._dist == 'normal':
-            return NormalDist(raw, self._min_std, self._max_std)
-        if self._dist == 'trunc_normal':
-            return TruncNormalDist(raw, self._min_std, self._init_std)
-        if self._dist == 'twohot':
-            return TwoHotDist(raw)
-        if self._dist == 'mse':
-            return MSEHeadDist(raw.reshape(list(inputs.shape[:-1]) + list(self._shape)))
-        if self._dist == 'onehot':
-            return OneHotDist(raw.float(), site='actor', independent=False)
-        raise NotImplementedError(self._dist)
+        return self._head.dist(self.raw(inputs))
 
 
 class MLP(Module):  # ref :718-747
@@ -525,15 +584,74 @@ class Decoder(Module):  # ref :631-715
 
 # ----------------------------------------------------------------------------- RSSM
 
-def _scan_noise(site, step_site, T, rows, K, dev, kind='exp'):
-    """Exp(1) noise (kind 'normal': N(0, 1), the continuous latents') of a whole scan, (T, rows, K).  Tests that replay the reference's
-    per-step draws inject them under the step site's name (one tensor per obs_step call, `rssm.post` / `rssm.prior`): those are stacked
-    in call order."""
-    inj = noise._injected
-    if inj is not None and site not in inj and step_site in inj:
-        return torch.stack([noise.draw(kind, step_site, (rows, K), dev) for _ in range(T)], 0)
-    return noise.draw(kind, site, (T, rows, K), dev)
+_tm = lambda x: x.transpose(0, 1).contiguous()          # (B, T, ..) -> (T, B, ..)
+_bm = lambda x: x.transpose(0, 1)                       # ... and back, as a view
 
+
+class _Latent:
+    """What EnsembleRSSM asks about its latent kind: _CatLatent or _NormalLatent, chosen once; a new kind is added as a third class.
+    fused: the batched observe, the C scans (ops.observe_seq, ops.rssm_imagine_seq) and the fused rollout exist for it.
+    scan_draw: a step-by-step scan draws its noise once and a step consumes its slice (False: a draw per step at the step's own site)."""
+    def zero_state(self, rows, dev):          # ref :355-359 (read-only constants, built once per shape)
+        return dict.fromkeys(self.stats + ('stoch',), _const((rows,) + self.shape, 0.0, dev))
+
+
+class _CatLatent(_Latent):
+    """`discrete: K`: S categorical latents of K classes with a 1 % uniform mix, one-hot samples; a head puts out their S x K logits"""
+    noise_kind, noise_suffix, stats, fused, scan_draw = 'exp', 'q', ('logit',), True, False
+
+    def __init__(self, stoch, discrete):
+        self.shape = (stoch, discrete)
+        self.head_width = self.stoch_size = stoch * discrete
+
+    def flat(self, stoch):
+        return stoch.reshape(list(stoch.shape[:-2]) + [self.stoch_size])
+
+    def noise_shape(self, lead):
+        return (int(np.prod(lead)) * self.shape[0], self.shape[1])
+
+    def head(self, raw, q, sample):           # a head's raw output -> stoch, stats; sample False: the mode
+        logit = raw.reshape(list(raw.shape[:-1]) + list(self.shape))
+        return (ops.onehot_sample(logit, q) if sample else ops.onehot_mode(logit)), {'logit': logit}
+
+    def dist(self, state):
+        return OneHotDist(state['logit'].float())
+
+    def unif_dist(self, state):
+        return OneHotDist(torch.ones_like(state['logit']), site='rssm.unif')
+
+    def kl(self, lhs, rhs, mix, free):        # mix max(KL(l || sg r), free).mean() + (1 - mix) max(KL(sg l || r), free).mean() as one node
+        return ops.kl_balance(lhs['logit'], rhs['logit'], mix, free)
+
+
+class _NormalLatent(_Latent):
+    """`discrete: False` (ref :333-335): S Normal latents, reparameterised samples; a head puts out [mean | std_raw]"""
+    noise_kind, noise_suffix, stats, fused, scan_draw = 'normal', 'eps', ('mean', 'std'), False, True
+
+    def __init__(self, stoch, std_act, min_std):
+        self.shape, self.std_act, self.min_std = (stoch,), std_act, min_std
+        self.head_width, self.stoch_size = 2 * stoch, stoch
+
+    def flat(self, stoch):
+        return stoch
+
+    def noise_shape(self, lead):
+        return tuple(lead) + self.shape
+
+    def head(self, raw, eps, sample):
+        """_suff_stats_layer + get_dist(stats).sample() (ref :513-521, :416-419).  sample False: stoch = mean -- what the reference's
+        prior falls back to (ref :483-486); its posterior calls `dist.mode()` without that guard (ref :456) and raises, see DESIGN 5g."""
+        mean, std, stoch = ops.gauss_head(raw, eps if sample else None, self.std_act, self.min_std)
+        return stoch, {'mean': mean, 'std': std}
+
+    def dist(self, state):
+        return LatentNormalDist(state['mean'].float(), state['std'].float())
+
+    def unif_dist(self, state):               # N(0, 1), ref :427-429
+        return LatentNormalDist(torch.zeros_like(state['mean']), torch.ones_like(state['std']), site='rssm.unif')
+
+    def kl(self, lhs, rhs, mix, free):        # the same node on Normal latents (torch's kl_normal_normal under Independent(., 1))
+        return ops.gauss_kl_balance(lhs['mean'], lhs['std'], rhs['mean'], rhs['std'], mix, free)
 
 
 class EnsembleRSSM(Module):  # ref :302-555
@@ -551,11 +669,10 @@ class EnsembleRSSM(Module):  # ref :302-555
         self._norm, self._cell_type, self.cell_input = norm, cell_type, cell_input
         self._std_act, self._min_std = std_act, min_std
         self.single_obs_posterior = single_obs_posterior
+        self._latent = _CatLatent(stoch, discrete) if self._discrete else _NormalLatent(stoch, std_act, min_std)
         self._cell = GRUCell(self._hidden, self._deter, norm=True, device=self.device)
-        # discrete latents: S x K logits; continuous (`discrete` False / 0, ref :333-335): [mean | std_raw] of S Normal latents
-        stats = stoch * discrete if discrete else 2 * stoch
-        self._ensemble_img_dist = nn.ModuleList([nn.Linear(hidden, stats) for _ in range(ensemble)])
-        self._obs_dist = nn.Linear(hidden, stats)
+        self._ensemble_img_dist = nn.ModuleList([nn.Linear(hidden, self._latent.head_width) for _ in range(ensemble)])
+        self._obs_dist = nn.Linear(hidden, self._latent.head_width)
         bias = norm != 'none'              # (a norm-free layer has no bias, ref :339-346; the GRU cell keeps its LayerNorm, ref :322)
         self._img_in = nn.Sequential(nn.Linear(self.get_stoch_size() + action_dim, hidden, bias=bias), NormLayer(norm, hidden))
         self._ensemble_img_out = nn.ModuleList(
@@ -565,15 +682,10 @@ class EnsembleRSSM(Module):  # ref :302-555
 
     # ---- shapes / helpers
     def initial(self, batch_size):
-        z = lambda *s: _zeros(tuple(s), self.device)        # (read-only constants, built once per shape)
-        if not self._discrete:                              # ref :355-359
-            return dict(mean=z(batch_size, self._stoch), std=z(batch_size, self._stoch), stoch=z(batch_size, self._stoch),
-                        deter=self._cell.get_initial_state(None, batch_size))
-        return dict(logit=z(batch_size, self._stoch, self._discrete), stoch=z(batch_size, self._stoch, self._discrete),
-                    deter=self._cell.get_initial_state(None, batch_size))
+        return dict(self._latent.zero_state(batch_size, self.device), deter=self._cell.get_initial_state(None, batch_size))
 
     def get_stoch_size(self):
-        return self._stoch * self._discrete if self._discrete else self._stoch
+        return self._latent.stoch_size
 
     def get_deter_size(self):
         return self._cell.state_size
@@ -582,10 +694,7 @@ class EnsembleRSSM(Module):  # ref :302-555
         return self.get_deter_size() + self.get_stoch_size()
 
     def get_stoch(self, state):
-        s = state['stoch']
-        if not self._discrete:
-            return s
-        return s.reshape(list(s.shape[:-2]) + [self._stoch * self._discrete])
+        return self._latent.flat(state['stoch'])
 
     def get_deter(self, state):
         return state['deter']
@@ -595,14 +704,19 @@ class EnsembleRSSM(Module):  # ref :302-555
 
     def get_dist(self, state, ensemble=False):
         assert not ensemble
-        if not self._discrete:
-            return LatentNormalDist(state['mean'].float(), state['std'].float())
-        return OneHotDist(state['logit'].float())
+        return self._latent.dist(state)
 
     def get_unif_dist(self, state):
-        if not self._discrete:                              # N(0, 1), ref :427-429
-            return LatentNormalDist(torch.zeros_like(state['mean']), torch.ones_like(state['std']), site='rssm.unif')
-        return OneHotDist(torch.ones_like(state['logit']), site='rssm.unif')
+        return self._latent.unif_dist(state)
+
+    def _scan_noise(self, site, step_site, T, B, dev):
+        """The latent noise of a T-step scan over B rows, one draw at `site` + '_q' / '_eps'.  Tests that replay the reference's per-step
+        draws inject them under the step site's name (one tensor per obs_step call, `rssm.post` / `rssm.prior`): stacked in call order."""
+        lat, inj = self._latent, noise._injected
+        site, shape = f'{site}_{lat.noise_suffix}', lat.noise_shape((B,))
+        if inj is not None and site not in inj and step_site in inj:
+            return torch.stack([noise.draw(lat.noise_kind, step_site, shape, dev) for _ in range(T)], 0)
+        return noise.draw(lat.noise_kind, site, (T,) + shape, dev)
 
     # ---- single steps (API parity; acting / data-free paths)
     def _prior_raw(self, deter):
@@ -624,44 +738,32 @@ class EnsembleRSSM(Module):  # ref :302-555
         lg = self._post_raw(embed, deter)
         return lg.reshape(list(lg.shape[:-1]) + [self._stoch, self._discrete])
 
-    def _gauss_stats(self, raw, sample, site, eps=None):
-        """_suff_stats_layer + get_dist(stats).sample() of the continuous branch (ref :513-521, :416-419) on a head's raw output
-        (..., 2S): -> stoch, {'mean', 'std'}.  sample False: stoch = mean -- what the reference's prior falls back to (ref :483-486);
-        its posterior calls `dist.mode()` without that guard (ref :456) and raises there, see DESIGN 5g.  eps: this step's slice of a
-        scan's noise, else drawn at `site`."""
+    def _sample_head(self, raw, sample, site, eps=None):     # eps: this step's slice of a scan's noise, else (when sampling) drawn at `site`
+        lat = self._latent
         if sample and eps is None:
-            eps = noise.draw('normal', site, tuple(raw.shape[:-1]) + (self._stoch,), raw.device)
-        mean, std, stoch = ops.gauss_head(raw, eps if sample else None, self._std_act, self._min_std)
-        return stoch, {'mean': mean, 'std': std}
+            eps = noise.draw(lat.noise_kind, site, lat.noise_shape(raw.shape[:-1]), raw.device)
+        return lat.head(raw, eps, sample)
 
     def get_stoch_stats_from_deter_state(self, temp_state, sample=True, site='rssm.prior', eps=None):
-        if not self._discrete:
-            return self._gauss_stats(self._prior_raw(temp_state['deter']), bool(sample), site, eps)
-        logit = self._prior_logits(temp_state['deter'])
-        d = OneHotDist(logit, site=site)
-        return (d.sample() if sample else d.mode()), {'logit': logit}
+        return self._sample_head(self._prior_raw(temp_state['deter']), bool(sample), site, eps)
 
     def img_step(self, prev_state, prev_action, sample=True, site='rssm.prior', eps=None):
+        """dense, GRU step, prior head, sample.  eps: the step's noise where a scan or a rollout drew it for all steps at once"""
         x = _dense_ln_silu(self.get_stoch(prev_state), self._img_in[0], self._img_in[1], prev_action)
         deter = ops.gru_step(x, prev_state['deter'], self._cell._layer.weight, self._cell._norm.weight,
                              self._cell._norm.bias)
-        # (eps: continuous latents inside a scan hand in the step's slice of the scan's noise)
-        stoch, stats = self.get_stoch_stats_from_deter_state({'deter': deter}, bool(sample), site, eps)
+        stoch, stats = self.get_stoch_stats_from_deter_state({'deter': deter}, sample, site, eps)
         return {'stoch': stoch, 'deter': deter, **stats}
 
     def get_post_stoch(self, embed, prior, should_sample=True, eps=None):
-        if not self._discrete:
-            return self._gauss_stats(self._post_raw(embed, prior['deter']), bool(should_sample), 'rssm.post', eps)
-        logit = self._post_logits(embed, prior['deter'])
-        d = OneHotDist(logit, site='rssm.post')
-        return (d.sample() if should_sample else d.mode()), {'logit': logit}
+        return self._sample_head(self._post_raw(embed, prior['deter']), bool(should_sample), 'rssm.post', eps)
 
     def obs_step(self, prev_state, prev_action, embed, is_first, should_sample=True, eps=None):
-        """eps: (prior, posterior) N(0, 1) noise of this step when a scan over continuous latents drew it for all steps at once"""
+        """eps: (prior, posterior) noise of this step when a scan drew it for all steps at once"""
         m = 1.0 - is_first.float()
         prev_state = {k: torch.einsum('b,b...->b...', m, v) for k, v in prev_state.items()}
         prev_action = torch.einsum('b,b...->b...', m, prev_action)
-        e_prior, e_post = eps if eps is not None else (None, None)
+        e_prior, e_post = eps or (None, None)
         prior = self.img_step(prev_state, prev_action, should_sample, eps=e_prior)
         stoch, stats = self.get_post_stoch(embed, prior, should_sample, e_post)
         return {'stoch': stoch, 'deter': prior['deter'], **stats}, prior
@@ -672,7 +774,7 @@ class EnsembleRSSM(Module):  # ref :302-555
         projection and the prior head are batched over all T steps; only h_{t-1} W_h + LN + gates is
         sequential (ops.gru_seq).  Without it, falls back to the step-by-step form."""
         B, T = action.shape[:2]
-        if not self._discrete:       # (continuous latents: the batched form and the C scan are built around the categorical sample)
+        if not self._latent.fused:
             return self._observe_stepwise(embed, action, is_first, state)
         if not self.single_obs_posterior:
             # (the scan's C launch loop has the LayerNorm launches of `norm: layer` built in: norm-free layers go step by step)
@@ -681,8 +783,7 @@ class EnsembleRSSM(Module):  # ref :302-555
             return self._observe_scan(embed, action, is_first, state)
         S, K = self._stoch, self._discrete
         dev = embed.device
-        tm = lambda x: x.transpose(0, 1).contiguous()                          # (B,T,..) -> (T,B,..)
-        emb, act, first = tm(embed), tm(action), tm(is_first)
+        emb, act, first = _tm(embed), _tm(action), _tm(is_first)
         mask = (1.0 - first.float()).contiguous()                              # (T,B)
         plog = self._post_logits(emb.reshape(T * B, -1)).reshape(T, B, S, K)
         pst = ops.onehot_sample(plog, noise.draw('exp', 'wm.post_q', (T, B * S, K), dev))
@@ -702,9 +803,8 @@ class EnsembleRSSM(Module):  # ref :302-555
                                 self._cell._norm.weight, self._cell._norm.bias)
             qlog = self._prior_logits(deter.reshape(T * B, -1)).reshape(T, B, S, K)
             qst = ops.onehot_sample(qlog, q_prior)
-        bm = lambda x: x.transpose(0, 1)
-        post = {'stoch': bm(pst), 'deter': bm(deter), 'logit': bm(plog)}
-        prior = {'stoch': bm(qst), 'deter': bm(deter), 'logit': bm(qlog)}
+        post = {'stoch': _bm(pst), 'deter': _bm(deter), 'logit': _bm(plog)}
+        prior = {'stoch': _bm(qst), 'deter': _bm(deter), 'logit': _bm(qlog)}
         return post, prior
 
     def _observe_scan(self, embed, action, is_first, state=None):
@@ -715,12 +815,11 @@ class EnsembleRSSM(Module):  # ref :302-555
         B, T = action.shape[:2]
         S, K = self._stoch, self._discrete
         dev = embed.device
-        tm = lambda x: x.transpose(0, 1).contiguous()                          # (B,T,..) -> (T,B,..)
-        emb, act, first = tm(embed), tm(action), tm(is_first)
+        emb, act, first = _tm(embed), _tm(action), _tm(is_first)
         mask = (1.0 - first.float()).contiguous()                              # (T,B)
         st0 = state if state is not None else self.initial(B)
-        q_post = _scan_noise('wm.post_q', 'rssm.post', T, B * S, K, dev)
-        q_prior = _scan_noise('wm.prior_q', 'rssm.prior', T, B * S, K, dev)
+        q_post = self._scan_noise('wm.post', 'rssm.post', T, B, dev)
+        q_prior = self._scan_noise('wm.prior', 'rssm.prior', T, B, dev)
         lin_i, ln_i = self._img_in[0], self._img_in[1]._layer
         lin_o, ln_o = self._obs_out[0], self._obs_out[1]._layer
         deter, plog, pst = ops.observe_seq(
@@ -729,21 +828,20 @@ class EnsembleRSSM(Module):  # ref :302-555
             lin_o.weight, lin_o.bias, ln_o.weight, ln_o.bias, self._obs_dist.weight, self._obs_dist.bias, ln_i.eps, ln_o.eps)
         qlog = self._prior_logits(deter.reshape(T * B, -1)).reshape(T, B, S, K)
         qst = ops.onehot_sample(qlog, q_prior)
-        bm = lambda x: x.transpose(0, 1)
-        post = {'stoch': bm(pst.reshape(T, B, S, K)), 'deter': bm(deter), 'logit': bm(plog.reshape(T, B, S, K))}
-        prior = {'stoch': bm(qst), 'deter': bm(deter), 'logit': bm(qlog)}
+        post = {'stoch': _bm(pst.reshape(T, B, S, K)), 'deter': _bm(deter), 'logit': _bm(plog.reshape(T, B, S, K))}
+        prior = {'stoch': _bm(qst), 'deter': _bm(deter), 'logit': _bm(qlog)}
         return post, prior
 
     def _observe_stepwise(self, embed, action, is_first, state=None):
         B, T = action.shape[:2]
         state = state if state is not None else self.initial(B)
         posts, priors = [], []
-        if not self._discrete:       # one draw per site for the whole scan (T, B, S); a step consumes its slice
-            e_prior = _scan_noise('wm.prior_eps', 'rssm.prior', T, B, self._stoch, embed.device, 'normal')
-            e_post = _scan_noise('wm.post_eps', 'rssm.post', T, B, self._stoch, embed.device, 'normal')
+        e_prior = e_post = [None] * T
+        if self._latent.scan_draw:
+            e_prior = self._scan_noise('wm.prior', 'rssm.prior', T, B, embed.device)
+            e_post = self._scan_noise('wm.post', 'rssm.post', T, B, embed.device)
         for t in range(T):
-            eps = (e_prior[t], e_post[t]) if not self._discrete else None
-            post, prior = self.obs_step(state, action[:, t], embed[:, t], is_first[:, t], eps=eps)
+            post, prior = self.obs_step(state, action[:, t], embed[:, t], is_first[:, t], eps=(e_prior[t], e_post[t]))
             posts.append(post); priors.append(prior); state = post
         st = lambda L: {k: torch.stack([d[k] for d in L], 1) for k in L[0]}
         return st(posts), st(priors)
@@ -752,31 +850,24 @@ class EnsembleRSSM(Module):  # ref :302-555
         """ref :373-381: prior rollout for given actions (B,T,A)."""
         B, T = action.shape[:2]
         state = state if state is not None else self.initial(B)
-        if not self._discrete:
-            eps = _scan_noise('rssm.imagine_eps', 'rssm.prior', T, B, self._stoch, action.device, 'normal') if sample else None
-            outs = []
-            for t in range(T):
-                state = self.img_step(state, action[:, t], sample, eps=eps[t] if sample else None)
-                outs.append(state)
-            return {k: torch.stack([d[k] for d in outs], 1) for k in outs[0]}
-        if (not torch.is_grad_enabled() and action.is_cuda and self._norm != 'none'
+        if (self._latent.fused and not torch.is_grad_enabled() and action.is_cuda and self._norm != 'none'
                 and os.environ.get('GENRL_OBSERVE_SEQ', '1') != '0'):
             # forward only (the data-free block's warm-up rollouts, report, video_imagine all run under no_grad): the action half of
             # `_img_in` batched over T, the eight launches per step of the remaining chain from ONE host call (csrc/seq.hip)
             S, K = self._stoch, self._discrete
             lin_i, ln_i = self._img_in[0], self._img_in[1]._layer
             lin_o, ln_o = self._ensemble_img_out[0][0], self._ensemble_img_out[0][1]._layer
-            q = _scan_noise('rssm.imagine_q', 'rssm.prior', T, B * S, K, action.device) if sample else None
+            q = self._scan_noise('rssm.imagine', 'rssm.prior', T, B, action.device) if sample else None
             deter, logit, stoch = ops.rssm_imagine_seq(
                 action.transpose(0, 1), state['stoch'].reshape(B, S * K), state['deter'], q, S, K,
                 lin_i.weight, lin_i.bias, ln_i.weight, ln_i.bias, self._cell._layer.weight, self._cell._norm.weight,
                 self._cell._norm.bias, lin_o.weight, lin_o.bias, ln_o.weight, ln_o.bias, self._ensemble_img_dist[0].weight,
                 self._ensemble_img_dist[0].bias, ln_i.eps, ln_o.eps)
-            bm = lambda x: x.transpose(0, 1)
-            return {'stoch': bm(stoch.reshape(T, B, S, K)), 'deter': bm(deter), 'logit': bm(logit.reshape(T, B, S, K))}
+            return {'stoch': _bm(stoch.reshape(T, B, S, K)), 'deter': _bm(deter), 'logit': _bm(logit.reshape(T, B, S, K))}
+        eps = self._scan_noise('rssm.imagine', 'rssm.prior', T, B, action.device) if sample and self._latent.scan_draw else [None] * T
         outs = []
         for t in range(T):
-            state = self.img_step(state, action[:, t], sample)
+            state = self.img_step(state, action[:, t], sample, eps=eps[t])
             outs.append(state)
         return {k: torch.stack([d[k] for d in outs], 1) for k in outs[0]}
 
@@ -786,11 +877,7 @@ class EnsembleRSSM(Module):  # ref :302-555
         assert balance != 0.5 and not free_avg
         lhs, rhs = (prior, post) if forward else (post, prior)
         mix = balance if forward else (1 - balance)
-        if not self._discrete:       # the same node on Normal latents (torch's kl_normal_normal under Independent(., 1))
-            return ops.gauss_kl_balance(lhs['mean'], lhs['std'], rhs['mean'], rhs['std'], mix, free)
-        l, r = lhs['logit'], rhs['logit']
-        # mix * max(KL(l || sg r), free).mean() + (1 - mix) * max(KL(sg l || r), free).mean() as one autograd node
-        return ops.kl_balance(l, r, mix, free)
+        return self._latent.kl(lhs, rhs, mix, free)
 
 
 # ----------------------------------------------------------------------------- optimiser
@@ -904,7 +991,7 @@ class Optimizer:
         ops.direct_grads = True        # weight-gradient kernels accumulate straight into the flat gradient buffers
         ops.defer_begin()              # ... and the LayerNorm backward passes leave their parameter-gradient partials unreduced
         try:
-            loss.backward(gradient=_one_like(loss))       # (a cached seed: torch would fill a fresh ones tensor per call)
+            loss.backward(gradient=_const(loss.shape, 1.0, loss.device, loss.dtype))       # (a cached seed: torch would fill a fresh ones tensor per call)
         except BaseException:
             ops.direct_grads = False
             ops.defer_abort()          # a failed backward pass: its partial sets (possibly never written) are NOT summed into the gradients

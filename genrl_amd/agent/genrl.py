@@ -72,9 +72,6 @@ class GenRLAgent(DreamerAgent):
         self.wm.grad_heads.append('reward')
         self._acting_behavior = self._imag_behavior
 
-    def update_wm(self, data, step):
-        return super().update_wm(data, step)
-
     # ------------------------------------------------------------------ reporting (agent/genrl.py:64-106)
     def report(self, data, key='observation', nvid=8):
         """Adds 'video_clip_pred': ground truth | reconstruction of the first chunk followed by the

@@ -951,43 +951,62 @@ def maxcos(u, v, urow=None):
 # ------------------------------------------------------------------ actor head
 
 class _ActorHead(Function):
+    """The sample of a Normal policy head from raw = [out | std_raw].  kind, _ACTOR_HEAD or _TRUNC_HEAD below: (C entry point pair, the
+    backward's pick from the two std parameters, what eps / the upstream gradient / mean_std's raw pass through)"""
     @staticmethod
-    def forward(ctx, raw, eps, min_std, max_std):
+    def forward(ctx, raw, eps, kind, p0, p1):
+        name, _, cast = kind
         r2 = _f32(raw).reshape(-1, raw.shape[-1]).contiguous()
-        R, A2 = r2.shape
-        A = A2 // 2
-        e = eps.reshape(R, A).contiguous()
+        R, A = r2.shape[0], r2.shape[1] // 2
+        e = cast(eps).reshape(R, A).contiguous()
         act = torch.empty(R, A, device=raw.device)
-        check(lib().genrl_actor_head_fwd(_p(r2), _p(e), _p(act), None, None, R, A, min_std, max_std, 0, _stream()),
-              'actor_head_fwd')
+        check(getattr(lib(), f'genrl_{name}_fwd')(_p(r2), _p(e), _p(act), None, None, R, A, p0, p1, 0, _stream()), f'{name}_fwd')
         ctx.save_for_backward(r2, e)
-        ctx.cfg = (min_std, max_std, raw.shape)
+        ctx.cfg = (kind, p0, p1, raw.shape)
         return act.reshape(*raw.shape[:-1], A)
 
     @staticmethod
     def backward(ctx, g):
         r2, e = ctx.saved_tensors
-        min_std, max_std, rshape = ctx.cfg
-        R, A2 = r2.shape
+        (name, bwd_params, cast), p0, p1, rshape = ctx.cfg
+        R, A = r2.shape[0], r2.shape[1] // 2
         d = torch.empty_like(r2)
-        check(lib().genrl_actor_head_bwd(_p(g.reshape(R, A2 // 2).contiguous()), _p(r2), _p(e), _p(d), R, A2 // 2,
-                                         min_std, max_std, 0, _stream()), 'actor_head_bwd')
-        return d.reshape(rshape), None, None, None
+        check(getattr(lib(), f'genrl_{name}_bwd')(_p(cast(g).reshape(R, A).contiguous()), _p(r2), _p(e), _p(d), R, A, *bwd_params(p0, p1), 0,
+                                                  _stream()), f'{name}_bwd')
+        return d.reshape(rshape), None, None, None, None
+
+
+def _actor_mean_std(raw, kind, p0, p1):
+    name, _, cast = kind
+    r2 = cast(raw.detach()).reshape(-1, raw.shape[-1]).contiguous()
+    R, A = r2.shape[0], r2.shape[1] // 2
+    mean = torch.empty(R, A, device=raw.device); std = torch.empty(R, A, device=raw.device)
+    check(getattr(lib(), f'genrl_{name}_fwd')(_p(r2), None, None, _p(mean), _p(std), R, A, p0, p1, 0, _stream()), f'{name}_fwd')
+    return mean.reshape(*raw.shape[:-1], A), std.reshape(*raw.shape[:-1], A)
+
+
+_ACTOR_HEAD = ('actor_head', lambda min_std, max_std: (min_std, max_std), lambda t: t)
+_TRUNC_HEAD = ('trunc_normal_head', lambda min_std, init_std: (init_std,), _f32)
 
 
 def actor_sample(raw, eps, min_std=0.1, max_std=1.0):
     """raw (...,2A)=[out|std_raw] -> action = tanh(out) + std*eps (Normal rsample)"""
-    return _ActorHead.apply(raw, eps, float(min_std), float(max_std))
+    return _ActorHead.apply(raw, eps, _ACTOR_HEAD, float(min_std), float(max_std))
 
 
 def actor_mean_std(raw, min_std=0.1, max_std=1.0):
-    r2 = raw.detach().reshape(-1, raw.shape[-1]).contiguous()
-    R, A2 = r2.shape
-    A = A2 // 2
-    mean = torch.empty(R, A, device=raw.device); std = torch.empty(R, A, device=raw.device)
-    check(lib().genrl_actor_head_fwd(_p(r2), None, None, _p(mean), _p(std), R, A, min_std, max_std, 0, _stream()),
-          'actor_head_fwd')
-    return mean.reshape(*raw.shape[:-1], A), std.reshape(*raw.shape[:-1], A)
+    return _actor_mean_std(raw, _ACTOR_HEAD, min_std, max_std)
+
+
+def trunc_normal_sample(raw, eps, min_std=0.1, init_std=0.0):
+    """raw (..., 2A) = [out | std_raw] -> clamp(tanh(out) + std eps, -1 + 1e-6, 1 - 1e-6) with the straight-through gradient of
+    TruncatedNormal.sample (tools/utils.py:102-123)"""
+    return _ActorHead.apply(raw, eps, _TRUNC_HEAD, float(min_std), float(init_std))
+
+
+def trunc_normal_mean_std(raw, min_std=0.1, init_std=0.0):
+    """-> tanh(out), 2 sigmoid((std_raw + init_std) / 2) + min_std (no gradient: acting, eval_policy, metrics)"""
+    return _actor_mean_std(raw, _TRUNC_HEAD, min_std, init_std)
 
 
 # ---- genrl_rollout_f32 (include/genrl_hip.h): the arguments of the fp32-operand rollout's launch loops in C (csrc/seq.hip)
@@ -2467,48 +2486,6 @@ class _DenseAct(Function):
 
 def dense_act(x1, x2, W):
     return _DenseAct.apply(x1, x2, W)
-
-
-class _TruncNormalHead(Function):
-    @staticmethod
-    def forward(ctx, raw, eps, min_std, init_std):
-        r2 = _f32(raw).reshape(-1, raw.shape[-1]).contiguous()
-        R, A2 = r2.shape
-        A = A2 // 2
-        e = _f32(eps).reshape(R, A).contiguous()
-        act = torch.empty(R, A, device=raw.device)
-        check(lib().genrl_trunc_normal_head_fwd(_p(r2), _p(e), _p(act), None, None, R, A, min_std, init_std, 0, _stream()),
-              'trunc_normal_head_fwd')
-        ctx.save_for_backward(r2, e)
-        ctx.cfg = (init_std, raw.shape)
-        return act.reshape(*raw.shape[:-1], A)
-
-    @staticmethod
-    def backward(ctx, g):
-        r2, e = ctx.saved_tensors
-        init_std, rshape = ctx.cfg
-        R, A2 = r2.shape
-        d = torch.empty_like(r2)
-        check(lib().genrl_trunc_normal_head_bwd(_p(_f32(g).reshape(R, A2 // 2).contiguous()), _p(r2), _p(e), _p(d), R, A2 // 2, init_std,
-                                                0, _stream()), 'trunc_normal_head_bwd')
-        return d.reshape(rshape), None, None, None
-
-
-def trunc_normal_sample(raw, eps, min_std=0.1, init_std=0.0):
-    """raw (..., 2A) = [out | std_raw] -> clamp(tanh(out) + std eps, -1 + 1e-6, 1 - 1e-6) with the straight-through gradient of
-    TruncatedNormal.sample (tools/utils.py:102-123)"""
-    return _TruncNormalHead.apply(raw, eps, float(min_std), float(init_std))
-
-
-def trunc_normal_mean_std(raw, min_std=0.1, init_std=0.0):
-    """-> tanh(out), 2 sigmoid((std_raw + init_std) / 2) + min_std (no gradient: acting, eval_policy, metrics)"""
-    r2 = _f32(raw.detach()).reshape(-1, raw.shape[-1]).contiguous()
-    R, A2 = r2.shape
-    A = A2 // 2
-    mean = torch.empty(R, A, device=raw.device); std = torch.empty(R, A, device=raw.device)
-    check(lib().genrl_trunc_normal_head_fwd(_p(r2), None, None, _p(mean), _p(std), R, A, min_std, init_std, 0, _stream()),
-          'trunc_normal_head_fwd')
-    return mean.reshape(*raw.shape[:-1], A), std.reshape(*raw.shape[:-1], A)
 
 
 class _SqErr(Function):
