@@ -336,7 +336,9 @@ class WorldModel(Module):  # ref :120-321
                        getattr(policy, f'norm{i}')._layer.eps) for i in range(policy._layers)]
             # (plane operands pay from ~512 rollout rows up: below, every product is launch-latency bound either way and
             # the plane writes only add traffic -- measured 14.2 vs 13.7 ms/step at 4 sequences per GPU)
-            tape = (ops_planes.ActorTapePlanes if common.planes_route(N) else ops.ActorTape)(horizon, N, layers, head_w, head_b, dev)
+            # (the plane tape is driven by the fused rollout alone: the step-by-step loop below reads every layer's fp32 output)
+            on_planes = common.planes_route(N) and not eval_policy and set(start) == {'stoch', 'deter', 'logit'}
+            tape = (ops_planes.ActorTapePlanes if on_planes else ops.ActorTape)(horizon, N, layers, head_w, head_b, dev)
             tape.head_leaves = (policy._out._out.weight, policy._out._out.bias, policy._out._std.weight, policy._out._std.bias)
         fused = tape is not None and not eval_policy and set(start) == {'stoch', 'deter', 'logit'}
         if fused:

@@ -467,9 +467,17 @@ class MLP(Module):  # ref :718-747
         consumed without materialising the concatenation.  planes: h2 planes of the inputs, if the caller has them."""
         x = features.reshape([-1, features.shape[-1]])
         x2 = features2.reshape([-1, features2.shape[-1]]) if features2 is not None else None
-        for index in range(self._layers):
-            x = _dense_ln_silu(x, getattr(self, f'dense{index}'), getattr(self, f'norm{index}'), x2, planes=planes)
-            x2 = planes = None
+        if (self._layers > 1 and self._norm != 'none'
+                and planes_route(x.shape[0], 'GENRL_PLANES_MLP', (self._units, x.shape[-1]), x.is_cuda)):
+            # every layer on plane operands: the whole chain as one node, which writes no fp32 copy of a hidden activation that only the
+            # next layer's plane product reads (ops_planes._TrunkPlanes) -- layer by layer the same launches as the loop below
+            layers = [(getattr(self, f'dense{i}').weight, getattr(self, f'dense{i}').bias, getattr(self, f'norm{i}')._layer.weight,
+                       getattr(self, f'norm{i}')._layer.bias, getattr(self, f'norm{i}')._layer.eps) for i in range(self._layers)]
+            x = ops_planes.dense_ln_trunk(x, x2, layers, planes=planes)
+        else:
+            for index in range(self._layers):
+                x = _dense_ln_silu(x, getattr(self, f'dense{index}'), getattr(self, f'norm{index}'), x2, planes=planes)
+                x2 = planes = None
         out = x.reshape(list(features.shape[:-1]) + [x.shape[-1]])
         h = getattr(x, '_planes', None)        # (reshape returns a new tensor object: carry the operand planes of the rows along)
         if h is not None:

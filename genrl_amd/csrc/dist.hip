@@ -197,7 +197,7 @@ __global__ __launch_bounds__(1024) void onehot_bwd_kernel(const float* __restric
   float o = 0.f;
   if (valid) {
     o = accumulate ? dlogits[gi * K + k] + d : d;
-    dlogits[gi * K + k] = o;
+    if (dlogits) dlogits[gi * K + k] = o;       // (NULL: planes only -- the launcher allows it without `accumulate` alone)
   }
   if (xo.p) {            // blockDim.x == rowlen == W * (groups per row), W == K: this workgroup is plane row blockIdx.x
     const float am = wave_max(fabsf(o));
@@ -650,6 +650,12 @@ int genrl_onehot_fwd_h2(const float* logits, const float* q, float* sample, floa
   return onehot_fwd_impl(logits, q, sample, probs, G, K, unimix, PlaneOut{sp, ldp, plane, inv}, rowlen, stream);
 }
 
+/* does the one-hot backward write the planes of d logits itself -- a plane row is one workgroup: K lanes per group (K a dispatch width),
+ * rowlen a multiple of 64, <= 1024 threads?  Then, without `accumulate`, dlogits may be NULL (planes only). */
+int genrl_onehot_bwd_planes_only_ok(int K, int rowlen) {
+  return (K == 4 || K == 8 || K == 16 || K == 32 || K == 64) && rowlen > 0 && rowlen % 64 == 0 && rowlen <= 1024 && rowlen % K == 0;
+}
+
 static int onehot_bwd_impl(const float* logits, const float* gsample, float* dlogits, long G, int K, float unimix,
                      int accumulate, PlaneOut xo, int rowlen, void* stream, MaskedGrad mg = MaskedGrad{nullptr, nullptr, 1}) {
   GENRL_ENTER();
@@ -660,7 +666,8 @@ static int onehot_bwd_impl(const float* logits, const float* gsample, float* dlo
     constexpr int W = decltype(w)::value;
     // planes straight from the kernel when a plane row is one workgroup (K == W lanes per group, rowlen a multiple of 64,
     // <= 1024 threads); otherwise a second pass over dlogits
-    const bool rowblk = xo.p && W == K && rowlen % 64 == 0 && rowlen <= 1024;
+    const bool rowblk = xo.p && genrl_onehot_bwd_planes_only_ok(K, rowlen);       // (implies W == K)
+    if (!dlogits && (accumulate || !rowblk)) return (int)GENRL_EINVAL;    // (no fp32 copy: only where this kernel writes the planes itself)
     if (rowblk)
       hipLaunchKernelGGL((onehot_bwd_kernel<W>), dim3((G * K) / rowlen), dim3(rowlen), 0, (hipStream_t)stream, logits,
                          gsample, dlogits, G, K, unimix, accumulate, xo, rowlen, mg);

@@ -103,6 +103,17 @@ struct LnEpi {
   unsigned* sync;                            // word 0: failure flag
 };
 
+// Optional second product of the 64x64 h2 kernel (PAIR instantiation, genrl_gemm_h2_pair): C (+)= A B^T and C1 (+)= A B1^T share the A operand
+// and K, and run as ONE launch over tn0 + tn1 column tiles.  A workgroup whose column tile belongs to product 1 swaps in that product's
+// (B, C, ldc, N, accumulate) before the tile's work starts: the K loop and the epilogue do not know.  nx > 0: the launch's XCD sub-blocks are nx wide
+// along n and both tile counts divide by nx -- every XCD then takes tn0 / nx column tiles of product 0 AND tn1 / nx of product 1 for its row
+// panels, so that a row panel of A is fetched by the same XCDs for both products (once per XCD instead of once per XCD and product).
+struct PairSel {
+  const u16* b; long b_ld, b_plane; const float* b_inv;
+  float* C; long ldc; int N, accumulate;
+  int tn0, nx;
+};
+
 // a / b for exact powers of two (exponent arithmetic; clamped to the normal range)
 __device__ __forceinline__ float pow2_ratio(float a, float b) {
   const int ea = (int)((__builtin_bit_cast(unsigned, a) >> 23) & 255u), eb = (int)((__builtin_bit_cast(unsigned, b) >> 23) & 255u);
@@ -121,13 +132,13 @@ template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_wai
 
 // TM x TN 32x32 blocks per wave (2x2 waves per workgroup); BK = 64 (TM*TN == 1) or 32; NACC class accumulators;
 // FMT 0: x3 (three bf16 planes, six products), 1: h2 (two fp16 planes of the row-scaled value, three products); NS LDS stages
-template <int TM, int TN, int BK, int NACC, int FMT, int NS, bool FOLD = true, bool CONV = false, int PF = 0, bool LNE = false>
-// (TM TN == 1 with a ring of TWO stages: 64.75 KiB of LDS and <= 256 registers -- two workgroups per CU, for launches of 257 .. 512
-// tiles, whose second round would otherwise wait for the first one's epilogues)
-__global__ __launch_bounds__(256, (TM * TN == 1 && NS == 2 && FMT == 1) ? 2 : 1) void gemm_planes_kernel(PlaneSeg s0, PlaneSeg s1, float* __restrict__ C, long ldc,
-                                                         const float* __restrict__ bias, int M, int N, int accumulate,
-                                                         int tiles_m, int tiles_n, int xcd_m, SampleEpi smp, ConvGather cg, LnEpi ln) {
+// The kernel's body: tile map, K loop, epilogue.  IS_PAIR: two products on one A operand (PairSel) -- the second __global__ entry below
+template <int TM, int TN, int BK, int NACC, int FMT, int NS, bool FOLD, bool CONV, int PF, bool LNE, bool IS_PAIR>
+__device__ __forceinline__ void gemm_planes_body(PlaneSeg s0, PlaneSeg s1, float* __restrict__ C, long ldc,
+                                                 const float* __restrict__ bias, int M, int N, int accumulate,
+                                                 int tiles_m, int tiles_n, int xcd_m, SampleEpi smp, ConvGather cg, LnEpi ln, PairSel pr) {
   static_assert(!LNE || (TM * TN == 1 && FMT == 1 && !CONV && PF == 0), "LayerNorm epilogue: 64x64 h2 tile");
+  static_assert(!IS_PAIR || (TM * TN == 1 && FMT == 1 && !CONV && PF == 0 && !LNE), "pair of products: 64x64 h2 tile");
   constexpr int BM = 64 * TM, BN = 64 * TN;
   static_assert(!(FMT == 1 && FOLD) || (BM == 64 && BN == 64), "segment fold: 64x64 h2 tile");
   constexpr int NPL = FMT ? 2 : 3, NPROD = FMT ? 3 : 6;
@@ -180,6 +191,22 @@ __global__ __launch_bounds__(256, (TM * TN == 1 && NS == 2 && FMT == 1) ? 2 : 1)
       bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
       tile_m = bid / tiles_n;
       tile_n = bid % tiles_n;
+    }
+  }
+  if constexpr (IS_PAIR) {                // column tile of the launch -> (product, column tile of the product); all workgroup-uniform
+    const int tn1 = tiles_n - pr.tn0;
+    bool second;
+    if (pr.nx > 0) {
+      const int sub_n = tiles_n / pr.nx, q0 = pr.tn0 / pr.nx, xn = tile_n / sub_n, jn = tile_n % sub_n;
+      second = jn >= q0;
+      tile_n = second ? xn * (tn1 / pr.nx) + jn - q0 : xn * q0 + jn;
+    } else {
+      second = tile_n >= pr.tn0;
+      if (second) tile_n -= pr.tn0;
+    }
+    if (second) {
+      s0.b = pr.b; s0.b_ld = pr.b_ld; s0.b_plane = pr.b_plane; s0.b_inv = pr.b_inv;
+      C = pr.C; ldc = pr.ldc; N = pr.N; accumulate = pr.accumulate;
     }
   }
   const int m0 = tile_m * BM, n0 = tile_n * BN;
@@ -773,6 +800,26 @@ __global__ __launch_bounds__(256, (TM * TN == 1 && NS == 2 && FMT == 1) ? 2 : 1)
     }
   }
   wait_vm<0>();                       // no DMA may be in flight into this workgroup's LDS when it exits
+}
+
+template <int TM, int TN, int BK, int NACC, int FMT, int NS, bool FOLD = true, bool CONV = false, int PF = 0, bool LNE = false>
+// (TM TN == 1 with a ring of TWO stages: 64.75 KiB of LDS and <= 256 registers -- two workgroups per CU, for launches of 257 .. 512
+// tiles, whose second round would otherwise wait for the first one's epilogues)
+__global__ __launch_bounds__(256, (TM * TN == 1 && NS == 2 && FMT == 1) ? 2 : 1) void gemm_planes_kernel(PlaneSeg s0, PlaneSeg s1, float* __restrict__ C, long ldc,
+                                                         const float* __restrict__ bias, int M, int N, int accumulate,
+                                                         int tiles_m, int tiles_n, int xcd_m, SampleEpi smp, ConvGather cg, LnEpi ln) {
+  gemm_planes_body<TM, TN, BK, NACC, FMT, NS, FOLD, CONV, PF, LNE, false>(s0, s1, C, ldc, bias, M, N, accumulate, tiles_m, tiles_n, xcd_m, smp, cg, ln,
+                                                                          PairSel{});
+}
+// ... and the same body as a pair of one-segment products on one A operand (genrl_gemm_h2_pair).  An overload whose last template argument
+// is a TYPE: every other instantiation keeps its signature and its symbol, and this one's still starts gemm_planes_kernel<TM, TN, BK, ...
+struct PairOfProducts {};
+template <int TM, int TN, int BK, int NACC, int FMT, int NS, typename PAIR>
+__global__ __launch_bounds__(256, 1) void gemm_planes_kernel(PlaneSeg s0, float* __restrict__ C, long ldc, int M, int N, int accumulate,
+                                                              int tiles_m, int tiles_n, int xcd_m, PairSel pr) {
+  static_assert(std::is_same<PAIR, PairOfProducts>::value, "the pair entry");
+  gemm_planes_body<TM, TN, BK, NACC, FMT, NS, true, false, 0, false, true>(s0, PlaneSeg{nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, nullptr}, C, ldc, nullptr, M, N,
+                                                                           accumulate, tiles_m, tiles_n, xcd_m, SampleEpi{}, ConvGather{}, LnEpi{}, pr);
 }
 
 // ---- 128x128 tile, h2 operands, PLANE-ALTERNATING half stages -------------------------------------------------------------------------
@@ -1730,6 +1777,22 @@ int genrl_split_h2_batch(const genrl_split_desc* d, int n, void* stream) {
   return GENRL_OK;
 }
 
+// The instantiation genrl_gemm_h2 runs an M x N product of K columns on (gemm_h2_impl and genrl_gemm_h2_pair both ask here, so that a pair's
+// tiles run what their own launches would): big = 128x128 tiles (from 2048 64-tiles up); else 64x64 tiles, `two` = the two-stage ring with two
+// workgroups per CU -- 257 .. 512 tiles (3200-row products of the 512-wide Dreamer-v3 rollout: 400 tiles) instead of two rounds of one
+// (GENRL_PLANES_2PER=0 / 1: never / always -- experiments).  Measured (scripts/two_per_cu.py, profiles/r05_two_per_cu.txt): 400 tiles
+// 14.0 -> 11.2 us (K 512), 26.9 -> 23.9 (K 1536); 800 tiles 25.8 -> 20.2; 1200 tiles K 1024 58 -> 53; but 256 tiles 11.2 -> 13.8 and 768 tiles
+// at K 2048 62 -> 64 (the two-stage ring is too shallow for long K loops on its own): from 257 tiles up while K <= 1536
+struct H2Route { bool big, two; };
+static H2Route h2_route(int M, int N, int K, bool sample) {
+  static const char* two_env = getenv("GENRL_PLANES_2PER");
+  const long t64 = (long)cdiv(M, 64) * cdiv(N, 64);
+  H2Route r;
+  r.big = sample ? false : (g_planes_force_tile ? g_planes_force_tile == 2 : t64 >= 2048);
+  r.two = !sample && (two_env ? two_env[0] == '1' : (t64 > 256 && K <= 1536));
+  return r;
+}
+
 /* The same product on h2 operands: C[m,n] = sum_seg ainv_seg[m] binv_seg[n] sum_k (h_a h_b + (h_a l_b + l_a h_b) / 2^11) */
 static int gemm_h2_impl(const uint16_t* a0, long a0_ld, long a0_plane, const float* a0_inv, const uint16_t* b0, long b0_ld, long b0_plane,
                         const float* b0_inv, int k0, const uint16_t* a1, long a1_ld, long a1_plane, const float* a1_inv,
@@ -1739,9 +1802,9 @@ static int gemm_h2_impl(const uint16_t* a0, long a0_ld, long a0_plane, const flo
   if (M <= 0 || N <= 0 || k0 <= 0 || (k0 & 63) || (k1 & 63) || k1 < 0) return GENRL_EINVAL;
   if ((a0_ld & 7) || (b0_ld & 7) || (k1 && ((a1_ld & 7) || (b1_ld & 7)))) return GENRL_EINVAL;
   PlaneSeg s0{a0, a0_ld, a0_plane, b0, b0_ld, b0_plane, k0, a0_inv, b0_inv}, s1{a1, a1_ld, a1_plane, b1, b1_ld, b1_plane, k1, a1_inv, b1_inv};
-  const long t64 = (long)cdiv(M, 64) * cdiv(N, 64);
   // (128x128 tiles for the 1024x3072 GRU products -- 192 tiles -- measured neutral in the step: 29.65 vs 29.72 ms)
-  const bool big = smp.q ? false : (g_planes_force_tile ? g_planes_force_tile == 2 : t64 >= 2048);
+  const H2Route rt = h2_route(M, N, k0 + k1, smp.q != nullptr);
+  const bool big = rt.big;
   if (big && !g_planes_force_tile) {
     // wave quantisation: one 128x128 tile per CU at a time, so 1088 tiles (17 x 1024 rows, N = 1024) take five rounds of
     // the 256 CUs -- 206 us against 146 for the 1024 tiles of 16384 rows.  When the last, partial round is small and made of
@@ -1789,16 +1852,9 @@ static int gemm_h2_impl(const uint16_t* a0, long a0_ld, long a0_plane, const flo
     log_launch("h2/64", M, N, k0 + k1, kk_bytes(M, N, k0 + k1));
 #define L64(NS_) gemm_planes_kernel<1, 1, 64, 3, 1, NS_, true><<<tm * tn, 256, 0, (hipStream_t)stream>>>( \
     s0, s1, C, ldc, bias, M, N, accumulate, tm, tn, xcd_split(tm, tn), smp, ConvGather{}, LnEpi{})
-    // 257 .. 512 tiles (3200-row products of the 512-wide Dreamer-v3 rollout: 400 tiles): two co-resident workgroups per CU on a
-    // two-stage ring instead of two rounds of one (GENRL_PLANES_2PER=0 / 1: never / always -- experiments)
-    static const char* two_env = getenv("GENRL_PLANES_2PER");
-    const long ntile = (long)tm * tn;
-    // measured (scripts/two_per_cu.py, profiles/r05_two_per_cu.txt): 400 tiles 14.0 -> 11.2 us (K 512), 26.9 -> 23.9 (K 1536); 800 tiles
-    // 25.8 -> 20.2; 1200 tiles K 1024 58 -> 53; but 256 tiles 11.2 -> 13.8 and 768 tiles at K 2048 62 -> 64 (the two-stage ring is too
-    // shallow for long K loops on its own): from 257 tiles up while K <= 1536
-    const bool two = two_env ? two_env[0] == '1' : (ntile > 256 && k0 + k1 <= 1536);
+    const bool two = rt.two;        // (h2_route: the two-stage ring, two workgroups per CU)
     route(smp.q ? GENRL_ROUTE_64_SAMPLE : (two ? GENRL_ROUTE_64_NS2 : GENRL_ROUTE_64_NS3));
-    if (two && !smp.q) L64(2);
+    if (two) L64(2);
     else L64(3);
 #undef L64
   }
@@ -1890,6 +1946,36 @@ int genrl_gemm_h2(const uint16_t* a0, long a0_ld, long a0_plane, const float* a0
   route_reset();
   return gemm_h2_impl(a0, a0_ld, a0_plane, a0_inv, b0, b0_ld, b0_plane, b0_inv, k0, a1, a1_ld, a1_plane, a1_inv, b1, b1_ld, b1_plane,
                       b1_inv, k1, C, ldc, bias, M, N, accumulate, stream, SampleEpi{});
+}
+
+/* Two products on ONE A operand in one launch: C0 (+)= A B0^T (M x N0) and C1 (+)= A B1^T (M x N1), one segment of k columns each, no bias
+ * (a backward's two dgrads of one gradient: the GRU's d h and d x).  Column tile t < N0 / 64 of the launch belongs to product 0, the rest to
+ * product 1; every tile runs genrl_gemm_h2's 64x64 tile body (three-stage ring) on its own product's (B, C, ldc, accumulate), so each C
+ * is bitwise what its own genrl_gemm_h2 launch gives.  GENRL_EINVAL -- the caller launches the two products itself -- unless N0 % 64 == 0
+ * and genrl_gemm_h2 would run BOTH products on that instantiation (fewer than 2048 64-tiles each, and not the two-stage ring of 257+ tiles
+ * with k <= 1536). */
+int genrl_gemm_h2_pair(const uint16_t* a, long a_ld, long a_plane, const float* a_inv, int k,
+                       const uint16_t* b0, long b0_ld, long b0_plane, const float* b0_inv, float* C0, long ldc0, int N0, int accumulate0,
+                       const uint16_t* b1, long b1_ld, long b1_plane, const float* b1_inv, float* C1, long ldc1, int N1, int accumulate1,
+                       int M, void* stream) {
+  GENRL_ENTER();
+  route_reset();
+  if (M <= 0 || N0 <= 0 || N1 <= 0 || k <= 0 || (k & 63) || (N0 & 63) || !a || !b0 || !b1 || !C0 || !C1) return GENRL_EINVAL;
+  if ((a_ld & 7) || (b0_ld & 7) || (b1_ld & 7)) return GENRL_EINVAL;
+  const int tm = cdiv(M, 64), tn0 = N0 / 64, tn1 = cdiv(N1, 64), tn = tn0 + tn1;
+  for (int i = 0; i < 2; ++i) {          // the route genrl_gemm_h2 takes for each product alone
+    const H2Route rt = h2_route(M, i ? N1 : N0, k, false);
+    if (rt.big || rt.two) return GENRL_EINVAL;
+  }
+  const PlaneSeg s0{a, a_ld, a_plane, b0, b0_ld, b0_plane, k, a_inv, b0_inv};
+  const int xm = xcd_split(tm, tn);
+  const int nx = xm > 0 ? 8 / xm : 0;
+  const PairSel pr{b1, b1_ld, b1_plane, b1_inv, C1, ldc1, N1, accumulate1, tn0, (nx > 0 && tn0 % nx == 0 && tn1 % nx == 0) ? nx : 0};
+  log_launch("h2/64", M, (long)N0 + N1, k, kk_bytes(M, (long)N0 + N1, k));
+  route(GENRL_ROUTE_64_NS3);
+  gemm_planes_kernel<1, 1, 64, 3, 1, 3, PairOfProducts><<<tm * tn, 256, 0, (hipStream_t)stream>>>(s0, C0, ldc0, M, N0, accumulate0, tm, tn, xm, pr);
+  GENRL_CHECK_LAUNCH();
+  return GENRL_OK;
 }
 
 /* Dense -> LayerNorm (-> SiLU) in ONE launch (LnEpi above): C = A0 B0^T (+ A1 B1^T) + bias as genrl_gemm_h2 (C keeps the pre-activation for the

@@ -1250,7 +1250,8 @@ __global__ __launch_bounds__(256) void gru_gates_bwd_blk_kernel(
     }
     const Sum2 r = block_sum2_256(s1, s2, red);
     const float m1 = r.a / N, m2 = r.b / N;
-    float4* dp = reinterpret_cast<float4*>(dpre + (long)row * N);
+    // (dpre == NULL: the planes below are the only copy -- a caller whose products read planes alone)
+    float4* dp = dpre ? reinterpret_cast<float4*>(dpre + (long)row * N) : nullptr;
 #pragma unroll
     for (int i = 0; i < DV; ++i) {
       const int j = threadIdx.x + i * 256;
@@ -1262,7 +1263,7 @@ __global__ __launch_bounds__(256) void gru_gates_bwd_blk_kernel(
           o.y = rstd * (dz[c][i].y * gam[c][i].y - m1 - xh[c][i].y * m2);
           o.z = rstd * (dz[c][i].z * gam[c][i].z - m1 - xh[c][i].z * m2);
           o.w = rstd * (dz[c][i].w * gam[c][i].w - m1 - xh[c][i].w * m2);
-          dp[c * dv + j] = o;
+          if (dp) dp[c * dv + j] = o;
           dz[c][i] = o;
         }
       }
@@ -1705,6 +1706,7 @@ static int gru_gates_bwd_impl(const float* dhout, long lddo, const float* dhout2
   if (ldpart <= 0) ldpart = D;
   if ((ldpart & 3) || ldpart < D) return GENRL_EINVAL;
   if (xo.p && (!xo.inv || (xo.ld & 3) || xo.ld < 3 * D)) return GENRL_EINVAL;
+  if (!dpre && !xo.p) return GENRL_EINVAL;      // (no fp32 copy is allowed only where the planes are written)
   if (!dhout2_parts) nparts = 0;
   if (nparts > 0 && (!dhout2 || !aligned16(dhout2_parts) || (part_stride & 3))) return GENRL_EINVAL;
   if ((D & 3) || D > 4096 || (ldh & 3) || (lddo & 3) || (lddh & 3) || !aligned16(pre) || !aligned16(h) ||

@@ -102,7 +102,7 @@ static inline int ln_h2(const float* pre, const float* g, const float* be, float
 #define RC(x) do { const int rc_ = (x); if (rc_) return rc_; } while (0)
 
 int genrl_imagine_seq_fwd(const genrl_rollout* r, void* st) {
-  if (!r || r->H <= 0 || r->N <= 0 || r->L < 1 || r->L > 8) return GENRL_EINVAL;
+  if (!r || r->H <= 0 || r->N <= 0 || r->L < 1 || r->L > 8 || !r->py[r->L - 1]) return GENRL_EINVAL;
   const int H = r->H, N = r->N, D = r->D, A = r->A, AP = r->AP, U = r->U, L = r->L;
   const long SK = (long)r->S * r->K;
   for (int h = 0; h < H; ++h) {
@@ -111,16 +111,17 @@ int genrl_imagine_seq_fwd(const genrl_rollout* r, void* st) {
     for (int l = 0; l < L; ++l) {
       const int Ul = r->pU[l];
       float* pre = r->ppre[l] + r0 * Ul;
+      float* const py_l = r->py[l] ? r->py[l] + r0 * Ul : nullptr;      // (NULL: a hidden layer consumed as planes only)
       if (r->ln_sync && genrl_gemm_h2_ln_ok(N, Ul)) {
         if (l == 0) RC(gemm2_ln(r, r->stoch_p, r0, r->pw0s, &r->deter_p, r0, &r->pw0d, pre, r->pb[0], N, Ul, r->pg[l], r->pbe[l], r->peps[l],
-                                r->py[l] + r0 * Ul, r->pmean[l] + r0, r->prstd[l] + r0, r->pyp[l], r0, st));
+                                py_l, r->pmean[l] + r0, r->prstd[l] + r0, r->pyp[l], r0, st));
         else RC(gemm2_ln(r, r->pyp[l - 1], r0, r->pw[l], nullptr, 0, nullptr, pre, r->pb[l], N, Ul, r->pg[l], r->pbe[l], r->peps[l],
-                         r->py[l] + r0 * Ul, r->pmean[l] + r0, r->prstd[l] + r0, r->pyp[l], r0, st));
+                         py_l, r->pmean[l] + r0, r->prstd[l] + r0, r->pyp[l], r0, st));
         continue;
       }
       if (l == 0) RC(gemm2(r->stoch_p, r0, r->pw0s, &r->deter_p, r0, &r->pw0d, pre, Ul, r->pb[0], N, Ul, st));
       else RC(gemm2(r->pyp[l - 1], r0, r->pw[l], nullptr, 0, nullptr, pre, Ul, r->pb[l], N, Ul, st));
-      RC(ln_h2(pre, r->pg[l], r->pbe[l], r->py[l] + r0 * Ul, r->pmean[l] + r0, r->prstd[l] + r0, N, Ul, r->peps[l], r->pyp[l], r0, st));
+      RC(ln_h2(pre, r->pg[l], r->pbe[l], py_l, r->pmean[l] + r0, r->prstd[l] + r0, N, Ul, r->peps[l], r->pyp[l], r0, st));
     }
     const bool fuse_u = r->ln_sync && genrl_gemm_h2_ln_ok(N, U);
     {
@@ -184,24 +185,40 @@ int genrl_imagine_seq_bwd(const genrl_rollout_bwd* r, void* st) {
     // grad wrt stoch_{h+1} (complete in ds[h+1]) -> logits (straight-through), plus any direct logit gradient
     if (r->dl_in && hipMemcpyAsync(r->dlg, r->dl_in + r1 * SK, sizeof(float) * N * SK, hipMemcpyDeviceToDevice, (hipStream_t)st) != hipSuccess)
       return GENRL_ELAUNCH;
-    RC(genrl_onehot_bwd_h2(r->logit + r1 * SK, r->ds + r1 * SK, r->dlg, (long)N * r->S, r->K, r->unimix, r->dl_in ? 1 : 0,
+    // (without an upstream logit gradient the product below is the only reader, and it reads the planes: no fp32 copy where the kernel
+    // writes the planes itself)
+    float* const dlg = (!r->dl_in && genrl_onehot_bwd_planes_only_ok(r->K, (int)SK)) ? nullptr : r->dlg;
+    RC(genrl_onehot_bwd_h2(r->logit + r1 * SK, r->ds + r1 * SK, dlg, (long)N * r->S, r->K, r->unimix, r->dl_in ? 1 : 0,
                            const_cast<uint16_t*>(r->dlg_p.p), (int)SK, r->dlg_p.ld, r->dlg_p.plane, const_cast<float*>(r->dlg_p.inv), st));
     RC(gemm1(r->dlg_p, r->wt_dist, r->dov, U, N, U, 0, st));
     RC(lnb_h2(r->dov, r->o_pre + r0 * U, r->out_g, r->out_be, r->om + r0, r->orr + r0, r->do_pre, N, U, r->dop_p, st));
     RC(gemm1(r->dop_p, r->wt_out, r->dd + r1 * D, D, N, D, 1, st));
     // GRU: upstream = dd[h+1] (+ the recurrent part from step h+1's GRU, held in `nxt`)
     RC(genrl_gru_gates_bwd_h2(r->dd + r1 * D, D, nxt, nullptr, r->g_pre + r0 * 3 * D, r->deter + r0 * D, D, r->gru_g, r->gru_be, r->gm + r0,
-                              r->gr + r0, r->dg_pre, cur, D, nullptr, nullptr, nullptr, N, D, 0, nullptr, 0, 0,
+                              r->gr + r0, nullptr, cur, D, nullptr, nullptr, nullptr, N, D, 0, nullptr, 0, 0,
                               const_cast<uint16_t*>(r->dg_p.p), r->dg_p.ld, r->dg_p.plane, const_cast<float*>(r->dg_p.inv), st));
-    RC(gemm1(r->dg_p, r->wt_g_h, cur, D, N, D, 1, st));
-    RC(gemm1(r->dg_p, r->wt_g_x, r->dx, U, N, U, 0, st));
-    RC(lnb_h2(r->dx, r->x_pre + r0 * U, r->in_g, r->in_be, r->xm + r0, r->xr + r0, r->dx_pre, N, U, r->dxp_p, st));
+    // (d g_pre exists as planes only: both of its readers are plane products)  The two dgrads share the A operand: one launch
+    const int rc_p = genrl_gemm_h2_pair(r->dg_p.p, r->dg_p.ld, r->dg_p.plane, r->dg_p.inv, (int)r->dg_p.ld,
+                                        r->wt_g_h.p, r->wt_g_h.ld, r->wt_g_h.plane, r->wt_g_h.inv, cur, D, D, 1,
+                                        r->wt_g_x.p, r->wt_g_x.ld, r->wt_g_x.plane, r->wt_g_x.inv, r->dx, U, U, 0, N, st);
+    if (rc_p == GENRL_EINVAL) {       // (a shape the pair form does not take: the two launches it replaces)
+      RC(gemm1(r->dg_p, r->wt_g_h, cur, D, N, D, 1, st));
+      RC(gemm1(r->dg_p, r->wt_g_x, r->dx, U, N, U, 0, st));
+    } else RC(rc_p);
+    // d x_pre: planes for the product, fp32 for the head's backward -- which nothing inside the loop waits for: with a slab per step
+    // (dx_pre_all) it runs once, behind the loop, over all H N rows
+    float* const dxp = r->dx_pre_all ? r->dx_pre_all + r0 * U : r->dx_pre;
+    RC(lnb_h2(r->dx, r->x_pre + r0 * U, r->in_g, r->in_be, r->xm + r0, r->xr + r0, dxp, N, U, r->dxp_p, st));
     RC(gemm1(r->dxp_p, r->wt_in_s, r->ds + r0 * SK, SK, N, (int)SK, 1, st));
     // d action_{h+1} = dx_pre W_a (+ upstream) and the head's backward -> d raw_h: one launch
-    RC(genrl_actor_head_linear_bwd(r->dx_pre, U, r->waT, r->dact_all ? r->dact_all + r1 * AP : nullptr, AP, r->raws + r0 * 2 * A,
-                                   r->eps + r0 * A, r->d_raw + r0 * 2 * A, N, U, A, r->min_std, r->max_std, st));
+    if (!r->dx_pre_all)
+      RC(genrl_actor_head_linear_bwd(r->dx_pre, U, r->waT, r->dact_all ? r->dact_all + r1 * AP : nullptr, AP, r->raws + r0 * 2 * A,
+                                     r->eps + r0 * A, r->d_raw + r0 * 2 * A, N, U, A, r->min_std, r->max_std, st));
     nxt = cur; cur = (cur == r->dha) ? r->dhb : r->dha;
   }
+  if (r->dx_pre_all)      // (row h N + n of every operand is step h's row n; the upstream action gradient of step h is row block h + 1)
+    RC(genrl_actor_head_linear_bwd(r->dx_pre_all, U, r->waT, r->dact_all ? r->dact_all + (long)N * AP : nullptr, AP, r->raws, r->eps, r->d_raw,
+                                   (long)H * N, U, A, r->min_std, r->max_std, st));
   return GENRL_OK;
 }
 

@@ -1068,12 +1068,16 @@ class ActorTape:
         self.head_w, self.head_b = head_w, head_b
         U = [l[0].shape[0] for l in layers]
         self.pre = [torch.empty(H, N, u, device=dev) for u in U]
-        self.y = [torch.empty(H, N, u, device=dev) for u in U]
+        self.y = [torch.empty(H, N, u, device=dev) if self._keeps_y(l) else None for l, u in enumerate(U)]
         self.mean = [torch.empty(H, N, device=dev) for _ in U]
         self.rstd = [torch.empty(H, N, device=dev) for _ in U]
         self.d_raw = torch.zeros(H, N, head_w.shape[0], device=dev)
         self.inputs = None                        # (x1 (H,N,K1), x2 (H,N,K2)) set by the caller after the rollout
         self.seen = 0
+
+    def _keeps_y(self, l):
+        """is layer l's output kept in fp32?  (here: always -- the next layer's product and weight gradient read it)"""
+        return True
 
     head_leaves = None      # (W_mean, b_mean, W_std, b_std): the leaf parameters head_w / head_b were stacked from (set by the caller)
 

@@ -49,7 +49,7 @@ class _RolloutBwdArgs(_ct.Structure):
                 + [(n, _FP) for n in ('logit', 'deter', 'raws', 'eps', 'x_pre', 'g_pre', 'o_pre', 'xm', 'xr', 'gm', 'gr', 'om', 'orr',
                                       'ds', 'dd', 'dl_in', 'dact_all', 'd_raw', 'dlg', 'dov', 'do_pre', 'dg_pre', 'dx', 'dx_pre', 'dha', 'dhb')]
                 + [(n, _PRef) for n in ('dlg_p', 'dop_p', 'dg_p', 'dxp_p', 'wt_dist', 'wt_out', 'wt_g_x', 'wt_g_h', 'wt_in_s')]
-                + [(n, _FP) for n in ('waT', 'out_g', 'out_be', 'gru_g', 'gru_be', 'in_g', 'in_be')])
+                + [(n, _FP) for n in ('waT', 'out_g', 'out_be', 'gru_g', 'gru_be', 'in_g', 'in_be', 'dx_pre_all')])
 
 
 def _pref(P):
@@ -75,6 +75,19 @@ class ActorTapePlanes(ops.ActorTape):
         super().__init__(H, N, layers, head_w, head_b, dev)
         self.yp = [planes.Planes(H * N, l[0].shape[0], dev) for l in layers]
 
+    def _keeps_y(self, l):
+        """The last layer's output is the head's input.  A hidden layer's fp32 copy has ONE reader -- the next layer's weight gradient, and only
+        where that product stays on the fp32-operand kernel (_backward: `not tn`): with it on planes the LayerNorm writes planes only (self.y[l]
+        is None), where its kernel can (the fused product + LayerNorm always can; the row kernel from 257 to 4096 columns)."""
+        if l == len(self.layers) - 1:
+            return True
+        U, Un = self.layers[l][0].shape[0], self.layers[l + 1][0].shape[0]
+        return not (planes.tn_ok(self.H * self.N, Un, U, U) and 256 < U <= 4096 and U % 4 == 0)
+
+    def _forward(self, *args, **kwargs):
+        # (the step-by-step form reads every layer's fp32 output and fills no planes: this tape is driven by imagine_rollout alone)
+        raise ops.GenrlHipError('ActorTapePlanes runs inside ops_planes.imagine_rollout only; the step-by-step rollout takes ops.ActorTape')
+
     def _forward_planes(self, t, sp_, dp_, out):
         """layer 0 input = rows t*N.. of the rollout's stoch / deter planes (sp_, dp_)"""
         N = self.N
@@ -98,7 +111,7 @@ class ActorTapePlanes(ops.ActorTape):
             else:
                 planes.gemm(Ap, planes.weight(W), pre, U, b, N, U, a_row0=row0, c_off=off)
             if not fuse:
-                _ln_fwd(pre.data_ptr() + 4 * off, gamma, beta, y.data_ptr() + 4 * off, self.mean[l].data_ptr() + 4 * t * N,
+                _ln_fwd(pre.data_ptr() + 4 * off, gamma, beta, (y.data_ptr() + 4 * off) if y is not None else None, self.mean[l].data_ptr() + 4 * t * N,
                         self.rstd[l].data_ptr() + 4 * t * N, N, U, eps, self.yp[l], row0)
             Ap = self.yp[l]
         if out is None:               # the caller runs the output layer fused with the Normal head (ActorTape.head_fused)
@@ -123,20 +136,28 @@ class ActorTapePlanes(ops.ActorTape):
         for l in range(len(self.layers) - 1, -1, -1):
             W, b, gamma, beta, eps = self.layers[l]
             U, K = W.shape
-            dpre = torch.empty(M, U, device=dev)
+            # weight gradients: on the same planes through the transposing kernel (genrl_gemm_h2_tn) from TN_MIN_ROWS rows up
+            tn = planes.tn_ok(M, U, K, K)
+            if l == 0:
+                sp_ = getattr(self, 'state_planes', None)
+                tn = tn and sp_ is not None and self.inputs[0].shape[-1] % 4 == 0
+            # the fp32 copy of the pre-activation gradient has one reader, the fp32-operand weight-gradient kernel: with that product on
+            # planes the LayerNorm backward writes planes only (as _DenseLNActPlanes.backward), where its kernel writes planes itself
+            planes_only = tn and 256 < U <= 4096 and U % 4 == 0
+            dpre = None if planes_only else torch.empty(M, U, device=dev)
             if dpre_p is None or dpre_p.cols != U:
                 dpre_p = planes.Planes(M, U, dev)
             g0, g1, g2, ws, acc_p, direct = _ln_param_targets(M, U, gamma, beta, b, dev, bias_optional=True)
             _ln_bwd(_p(dy), _p(self.pre[l]), gamma, beta, _p(self.mean[l]), _p(self.rstd[l]), _p(dpre), M, U, dpre_p, 0,
                     g0, g1, g2, ws, acc_p)
             tw, acc, dW = _wgrad_target(W)
-            # weight gradients: on the same planes through the transposing kernel (genrl_gemm_h2_tn) from TN_MIN_ROWS rows up
-            tn = planes.tn_ok(M, U, K, K)
             if l > 0:
                 x = self.y[l - 1]
                 if tn:
                     planes.gemm_tn(dpre_p, self.yp[l - 1], tw, K, U, K, M, accumulate=acc)
                 else:
+                    # (_keeps_y decided at construction with the same tn_ok: the two can part only if the switches changed in between)
+                    assert x is not None, 'the fp32 input of a weight gradient on the fp32-operand kernel was not kept (tn_ok changed since the tape was built)'
                     sgemm(dpre, 1, U, x, 1, K, tw, K, None, U, K, M, accumulate=acc)
                 dy = torch.empty(M, K, device=dev)
                 planes.gemm(dpre_p, planes.weight(W, transpose=True), dy, K, None, M, K)
@@ -144,8 +165,7 @@ class ActorTapePlanes(ops.ActorTape):
                 x1, x2 = self.inputs
                 K1, K2 = x1.shape[-1], x2.shape[-1]
                 assert x1.is_contiguous() and x2.is_contiguous() and x1.shape[0] >= H and K1 + K2 == K
-                sp_ = getattr(self, 'state_planes', None)
-                if tn and sp_ is not None and K1 % 4 == 0:
+                if tn:
                     planes.gemm_tn(dpre_p, sp_[0], tw, K, U, K1, M, accumulate=acc)
                     planes.gemm_tn(dpre_p, sp_[1], tw, K, U, K2, M, accumulate=acc, c_off=K1)
                 else:
@@ -283,7 +303,12 @@ class _RolloutPlanes(Function):
         da_in = d_action.contiguous() if d_action is not None else None
         # (d o_pre is consumed as planes only: the LayerNorm backward writes no fp32 copy of it where its kernel can do without)
         no_dx = 256 < U <= 4096 and U % 4 == 0
-        dlg, do, do_pre, dg_pre, dx, dx_pre = f(N, SK), f(N, U), (None if no_dx else f(N, U)), f(N, 3 * D), f(N, U), f(N, U)
+        # (d g_pre has plane readers only -- the two GRU dgrads -- and so has d logits unless an upstream logit gradient is accumulated into
+        # its fp32 copy: neither is written in fp32 where the kernel writes the planes itself, csrc/dist.hip onehot_bwd_impl)
+        no_dlg = dl_in is None and lib().genrl_onehot_bwd_planes_only_ok(K, SK) == 1
+        dlg, do, do_pre, dx = (None if no_dlg else f(N, SK)), f(N, U), (None if no_dx else f(N, U)), f(N, U)
+        # d x_pre of EVERY step: the head's backward, which nothing in the loop waits for, then runs once over all H N rows behind it
+        dx_pre = f(H, N, U)
         dlg_p, dop_p, dg_p, dxp_p = planes.Planes(N, SK, dev), planes.Planes(N, U, dev), planes.Planes(N, 3 * D, dev), planes.Planes(N, U, dev)
         dha, dhb = f(N, D), f(N, D)
         cur, nxt = dha, None                              # ping-pong: recurrent gradient into deter_h from step h's GRU
@@ -307,7 +332,8 @@ class _RolloutPlanes(Function):
             for n_, t_ in (('logit', logit), ('deter', deter), ('raws', raws), ('eps', eps), ('x_pre', x_pre), ('g_pre', g_pre), ('o_pre', o_pre),
                            ('xm', st['xm']), ('xr', st['xr']), ('gm', st['gm']), ('gr', st['gr']), ('om', st['om']), ('orr', st['or']),
                            ('ds', ds), ('dd', dd), ('dl_in', dl_in), ('dact_all', dact_all), ('d_raw', tape.d_raw), ('dlg', dlg), ('dov', do),
-                           ('do_pre', do_pre), ('dg_pre', dg_pre), ('dx', dx), ('dx_pre', dx_pre), ('dha', dha), ('dhb', dhb), ('waT', waT),
+                           ('do_pre', do_pre), ('dg_pre', None), ('dx', dx), ('dx_pre', None), ('dx_pre_all', dx_pre), ('dha', dha), ('dhb', dhb),
+                           ('waT', waT),
                            ('out_g', sp.out_g), ('out_be', sp.out_be), ('gru_g', sp.gru_g), ('gru_be', sp.gru_be), ('in_g', sp.in_g),
                            ('in_be', sp.in_be)):
                 setattr(a, n_, _p(t_))
@@ -328,19 +354,20 @@ class _RolloutPlanes(Function):
             # GRU: upstream = dd[h+1] (+ recurrent part from step h+1's GRU, held in `nxt`)
             check(L.genrl_gru_gates_bwd_h2(pt(dd, r1 * D), D, nxt.data_ptr() if nxt is not None else None, None,
                                            pt(g_pre, h * N * 3 * D), pt(deter, r0 * D), D, _p(sp.gru_g), _p(sp.gru_be),
-                                           pt(st['gm'], r0), pt(st['gr'], r0), _p(dg_pre), _p(cur), D, None, None, None, N, D,
+                                           pt(st['gm'], r0), pt(st['gr'], r0), None, _p(cur), D, None, None, None, N, D,
                                            0, None, 0, 0, dg_p.ptr(), dg_p.ld, dg_p.plane, dg_p.inv_ptr(), _stream()),
                   'gru_gates_bwd_h2')
-            planes.gemm(dg_p, wt_g_h, cur, D, None, N, D, accumulate=True)
-            planes.gemm(dg_p, wt_g_x, dx, U, None, N, U)
-            _ln_bwd(_p(dx), pt(x_pre, h * N * U), sp.in_g, sp.in_be, pt(st['xm'], r0), pt(st['xr'], r0), _p(dx_pre), N, U,
+            # the two GRU dgrads share their A operand: one launch (d h accumulates into `cur`, d x overwrites)
+            planes.gemm_pair(dg_p, wt_g_h, cur, D, D, True, wt_g_x, dx, U, U, False, N)
+            _ln_bwd(_p(dx), pt(x_pre, h * N * U), sp.in_g, sp.in_be, pt(st['xm'], r0), pt(st['xr'], r0), pt(dx_pre, h * N * U), N, U,
                     dxp_p, 0)
             planes.gemm(dxp_p, wt_in_s, ds, SK, None, N, SK, accumulate=True, c_off=r0 * SK)
-            # d action_{h+1} = dx_pre W_a (+ upstream) and the head's backward -> d raw_h: one launch
-            check(L.genrl_actor_head_linear_bwd(_p(dx_pre), U, _p(waT), pt(dact_all, r1 * AP) if dact_all is not None else None, AP,
-                                                pt(raws, h * N * 2 * A), pt(eps, h * N * A), pt(tape.d_raw, h * N * 2 * A), N, U, A,
-                                                sp.min_std, sp.max_std, _stream()), 'actor_head_linear_bwd')
             nxt, cur = cur, (dhb if cur is dha else dha)
+        if not seq_c:
+            # d action_{h+1} = dx_pre W_a (+ upstream) and the head's backward -> d raw_h, all H steps in one launch (rows h N + n)
+            check(L.genrl_actor_head_linear_bwd(_p(dx_pre), U, _p(waT), pt(dact_all, N * AP) if dact_all is not None else None, AP,
+                                                _p(raws), _p(eps), _p(tape.d_raw), H * N, U, A, sp.min_std, sp.max_std, _stream()),
+                  'actor_head_linear_bwd')
         if d_raws is not None:
             tape.d_raw += d_raws
         dWh, dbh, grads = tape._backward()
@@ -509,25 +536,168 @@ def min_rows():
     return int(os.environ.get('GENRL_PLANES_MIN_ROWS', MIN_ROWS_PLANES))
 
 
+def _ln_input_handles(x1, x2, planes_):
+    """(P1, r1), (P2, r2) of dense_ln_act's inputs: the caller's ((P1, row0), (P2, row0) | None), else the inputs' own `_planes` attribute
+    (a previous layer's output); dropped where they do not cover the rows -- and both where the second input comes without"""
+    M = x1.numel() // x1.shape[-1]
+    if planes_ is None:
+        h1 = getattr(x1, '_planes', None)
+        h2 = getattr(x2, '_planes', None) if x2 is not None else None
+    else:
+        h1, h2 = planes_[0], (planes_[1] if len(planes_) > 1 else None)
+    if h1 is not None and (h1[0].cols != x1.shape[-1] or h1[1] + M > h1[0].rows):
+        h1 = None
+    if x2 is not None and (h2 is None or h2[0].cols != x2.shape[-1] or h2[1] + M > h2[0].rows):
+        h1 = h2 = None
+    return (h1 if h1 is not None else (None, 0)), (h2 if h2 is not None else (None, 0))
+
+
 def dense_ln_act(x1, x2, W, b, gamma, beta, eps=1e-5, planes=None):
     """-> y with y._planes = (planes of y, 0) for the next layer.  planes = ((P1, row0), (P2, row0) | None) of the inputs when the
     caller has them (rollout states); otherwise the inputs' own `_planes` attribute (a previous layer's output) is used."""
     M = x1.numel() // x1.shape[-1]
     N = W.shape[0]
-    if planes is None:
-        h1 = getattr(x1, '_planes', None)
-        h2 = getattr(x2, '_planes', None) if x2 is not None else None
-    else:
-        h1, h2 = planes[0], (planes[1] if len(planes) > 1 else None)
-    if h1 is not None and (h1[0].cols != x1.shape[-1] or h1[1] + M > h1[0].rows):
-        h1 = None
-    if x2 is not None and (h2 is None or h2[0].cols != x2.shape[-1] or h2[1] + M > h2[0].rows):
-        h1 = h2 = None
-    P1, r1 = h1 if h1 is not None else (None, 0)
-    P2, r2 = h2 if h2 is not None else (None, 0)
+    (P1, r1), (P2, r2) = _ln_input_handles(x1, x2, planes)
     out_p = pl.Planes(M, N, x1.device)
     y = _DenseLNActPlanes.apply(x1, x2, W, b, gamma, beta, float(eps), P1, r1, P2, r2, out_p)
     y._planes = (out_p, 0)
+    return y
+
+
+class _TrunkPlanes(Function):
+    """A chain of _DenseLNActPlanes layers (an MLP trunk: agent/dreamer_utils.py:739-747) as ONE autograd node, the way ActorTapePlanes
+    treats the policy: the same launches in the same order, forward and backward, as the per-layer chain -- bit-identical outputs and
+    gradients, the same accumulation order into the flat gradient buffers -- but a hidden layer's output is consumed inside the node, as
+    planes, so its fp32 copy is written only where somebody reads it: the NEXT layer's weight gradient while it stays on the fp32-operand
+    kernel (below planes.tn_min_rows() rows), or a LayerNorm kernel that cannot write planes without it.  No tensor with undefined contents
+    leaves the node: the caller gets the last layer's fp32 output alone.  params: (W, b, gamma, beta) per layer; out_ps: the output planes
+    per layer; P1 / P2 (+ first rows): the planes of layer 0's inputs, or None."""
+    @staticmethod
+    def forward(ctx, x1, x2, P1, r1, P2, r2, eps, out_ps, *params):
+        a = _f32(x1).reshape(-1, x1.shape[-1]).contiguous()
+        c = _f32(x2).reshape(-1, x2.shape[-1]).contiguous() if x2 is not None else None
+        M, K1 = a.shape
+        K2 = c.shape[1] if c is not None else 0
+        L = len(out_ps)
+        dev = a.device
+        needs_w = [ctx.needs_input_grad[8 + 4 * l] for l in range(L)]
+        pres, means, rstds, ys, in_planes = [], [], [], [], []
+        for l in range(L):
+            W, b, gamma, beta = params[4 * l:4 * l + 4]
+            N, K = W.shape
+            if l == 0:
+                assert K == K1 + K2
+                Pa, ra, Pb, rb, k1, k2 = P1, r1, P2, r2, K1, K2
+            else:
+                Pa, ra, Pb, rb, k1, k2 = out_ps[l - 1], 0, None, 0, K, 0
+            two = l == 0 and c is not None
+            # the fp32 copy of this layer's output: the node's result (last layer), else see the class comment
+            keep_y = l == L - 1 or not (256 < N <= 4096 and N % 4 == 0
+                                        and (not needs_w[l + 1] or planes.tn_ok(M, params[4 * (l + 1)].shape[0], N, N)))
+            pre = torch.empty(M, N, device=dev)
+            y = torch.empty(M, N, device=dev) if keep_y else None
+            mean = torch.empty(M, device=dev); rstd = torch.empty(M, device=dev)
+            on_planes = Pa is not None and (not two or Pb is not None)
+            if on_planes and planes.gemm_ln_ok(M, N, dev):
+                if not two:
+                    planes.gemm_ln(Pa, planes.weight(W), pre, b, M, N, gamma, beta, eps[l], out_ps[l], 0, y=y, mean=mean, rstd=rstd, a_row0=ra)
+                else:
+                    planes.gemm_ln(Pa, planes.weight(W, c0=0, c1=k1), pre, b, M, N, gamma, beta, eps[l], out_ps[l], 0, y=y, mean=mean, rstd=rstd,
+                                   a_row0=ra, A1=Pb, B1=planes.weight(W, c0=k1), a1_row0=rb)
+            else:
+                if on_planes:
+                    if not two:
+                        planes.gemm(Pa, planes.weight(W), pre, N, b, M, N, a_row0=ra)
+                    else:
+                        planes.gemm(Pa, planes.weight(W, c0=0, c1=k1), pre, N, b, M, N, a_row0=ra, A1=Pb, B1=planes.weight(W, c0=k1), a1_row0=rb)
+                else:                    # (layer 0 alone: an input that came without planes)
+                    w1, ld1 = ops._aligned_block(W, k1, M)
+                    sgemm(a, k1, 1, w1, ld1, 1, pre, N, b, M, N, k1)
+                    if two:
+                        sgemm(c, k2, 1, W, K, 1, pre, N, None, M, N, k2, accumulate=True, b_off=k1)
+                _ln_fwd(_p(pre), gamma, beta, _p(y), _p(mean), _p(rstd), M, N, eps[l], out_ps[l], 0)
+            # the inputs' planes serve the weight gradient again (genrl_gemm_h2_tn): kept only when that product will really take them
+            keep = (on_planes and needs_w[l] and planes.tn_ok(M, N, k1, K) and (not two or k2 % 4 == 0) and ra % 4 == 0 and rb % 4 == 0)
+            in_planes.append(((Pa, ra), (Pb, rb)) if keep else None)
+            pres.append(pre); means.append(mean); rstds.append(rstd); ys.append(y)
+        ctx.save_for_backward(a, c if c is not None else a.new_empty(0), *params[0::4], *params[2::4], *params[3::4])
+        ctx.biases = list(params[1::4])
+        ctx.has2, ctx.L = c is not None, L
+        ctx.pres, ctx.means, ctx.rstds, ctx.in_planes = pres, means, rstds, in_planes
+        ctx.hidden_y = ys[:-1]                  # fp32 copies of the hidden activations that have a reader (None: planes only)
+        ctx.shapes = (x1.shape, x2.shape if x2 is not None else None)
+        return ys[-1].reshape(*x1.shape[:-1], ys[-1].shape[1])
+
+    @staticmethod
+    def backward(ctx, dy):
+        saved = ctx.saved_tensors
+        L = ctx.L
+        a, c = saved[0], saved[1]
+        Ws, gammas, betas = saved[2:2 + L], saved[2 + L:2 + 2 * L], saved[2 + 2 * L:2 + 3 * L]
+        ng = ctx.needs_input_grad
+        M, K1_0 = a.shape
+        dev = dy.device
+        out = [None] * (8 + 4 * L)
+        dyl = dy.reshape(M, Ws[-1].shape[0]).contiguous()
+        for l in range(L - 1, -1, -1):
+            W, gamma, beta, b = Ws[l], gammas[l], betas[l], ctx.biases[l]
+            N, K = W.shape
+            has2 = l == 0 and ctx.has2
+            K1 = K1_0 if l == 0 else K
+            K2 = K - K1
+            need_w, need_b, need_g = ng[8 + 4 * l], ng[9 + 4 * l], ng[10 + 4 * l]
+            # (what the per-layer chain's node sees as its input's requires_grad: anything upstream of this layer that wants a gradient)
+            need_x1 = ng[0] if l == 0 else (ng[0] or ng[1] or any(ng[8:8 + 4 * l]))
+            ip = ctx.in_planes[l]
+            use_tn = ip is not None and planes.tn_ok(M, N, K1, K) and (not has2 or K2 % 4 == 0)
+            planes_only = 256 < N <= 4096 and N % 4 == 0          # (the LayerNorm kernels that write planes themselves)
+            dpre = torch.empty(M, N, device=dev) if ((need_w and not use_tn) or not planes_only) else None
+            dpre_p = planes.Planes(M, N, dev)
+            need_p = need_w or need_b or need_g
+            g0, g1, g2, ws, acc_p, direct = _ln_param_targets(M, N, gamma, beta, b, dev, need=need_p)
+            _ln_bwd(_p(dyl), _p(ctx.pres[l]), gamma, beta, _p(ctx.means[l]), _p(ctx.rstds[l]), _p(dpre), M, N, dpre_p, 0, g0, g1, g2, ws, acc_p)
+            d1 = d2 = dW = None
+            if need_x1:
+                d1 = torch.empty(M, K1, device=dev)
+                planes.gemm(dpre_p, planes.weight(W, True, 0, K1), d1, K1, None, M, K1)
+            if has2 and ng[1]:
+                d2 = torch.empty(M, K2, device=dev)
+                planes.gemm(dpre_p, planes.weight(W, True, K1), d2, K2, None, M, K2)
+            if need_w:
+                tgt, acc, dW = _wgrad_target(W)
+                if use_tn:
+                    planes.gemm_tn(dpre_p, ip[0][0], tgt, K, N, K1, M, accumulate=acc, b_row0=ip[0][1])
+                    if has2:
+                        planes.gemm_tn(dpre_p, ip[1][0], tgt, K, N, K2, M, accumulate=acc, b_row0=ip[1][1], c_off=K1)
+                else:
+                    xin = a if l == 0 else ctx.hidden_y[l - 1]
+                    assert xin is not None, 'the fp32 input of a weight gradient on the fp32-operand kernel was not kept'
+                    sgemm(dpre, 1, N, xin, 1, K1, tgt, K, None, N, K1, M, accumulate=acc)
+                    if has2:
+                        sgemm(dpre, 1, N, c, 1, K2, tgt, K, None, N, K2, M, accumulate=acc, c_off=K1)
+            if need_p and not direct:
+                out[8 + 4 * l:12 + 4 * l] = [dW, (g2 if b is not None else None), g0, g1]
+            else:
+                out[8 + 4 * l] = dW
+            if l == 0:
+                out[0] = d1.reshape(ctx.shapes[0]) if d1 is not None else None
+                out[1] = d2.reshape(ctx.shapes[1]) if d2 is not None else None
+            dyl = d1
+            if dyl is None:          # (nothing upstream wants a gradient: the per-layer chain stops here too)
+                break
+        return tuple(out)
+
+
+def dense_ln_trunk(x1, x2, layers, planes=None):
+    """layers: [(W, b, gamma, beta, eps), ...] of a Dense -> LayerNorm -> SiLU chain whose first layer reads [x1, x2] (x2 may be None).
+    -> the last layer's output, with its `_planes` for the head's product; the same values and gradients as dense_ln_act layer by layer
+    (see _TrunkPlanes); `planes` as dense_ln_act's"""
+    M = x1.numel() // x1.shape[-1]
+    (P1, r1), (P2, r2) = _ln_input_handles(x1, x2, planes)
+    out_ps = [pl.Planes(M, l[0].shape[0], x1.device) for l in layers]
+    flat = [q for l in layers for q in l[:4]]
+    y = _TrunkPlanes.apply(x1, x2, P1, r1, P2, r2, [float(l[4]) for l in layers], out_ps, *flat)
+    y._planes = (out_ps[-1], 0)
     return y
 
 

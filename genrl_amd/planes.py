@@ -188,6 +188,22 @@ def gemm(A, B, C, ldc, bias, M, N, accumulate=False, a_row0=0, A1=None, B1=None,
     timed_end(gemm_profile, e0, M, N, A.cols + (A1.cols if A1 is not None else 0), 'kk/h2/pipe4')
 
 
+def gemm_pair(A, B0, C0, ldc0, N0, acc0, B1, C1, ldc1, N1, acc1, M):
+    """C0[M, N0] (+)= A B0^T and C1[M, N1] (+)= A B1^T: two products on one A operand as ONE launch (genrl_gemm_h2_pair) where the
+    kernel takes the shapes, else as the two genrl_gemm_h2 launches -- bit-identical either way"""
+    assert A.ld == B0.ld == B1.ld and M <= A.rows and N0 <= B0.rows and N1 <= B1.rows
+    e0 = timed_start(gemm_profile)
+    rc = lib().genrl_gemm_h2_pair(A.ptr(0), A.ld, A.plane, A.inv_ptr(0), A.ld,
+                                  B0.ptr(0), B0.ld, B0.plane, B0.inv_ptr(0), C0.data_ptr(), ldc0, N0, int(acc0),
+                                  B1.ptr(0), B1.ld, B1.plane, B1.inv_ptr(0), C1.data_ptr(), ldc1, N1, int(acc1), M, _stream())
+    if rc == 1:              # GENRL_EINVAL: a shape the pair form does not take
+        gemm(A, B0, C0, ldc0, None, M, N0, accumulate=acc0)
+        gemm(A, B1, C1, ldc1, None, M, N1, accumulate=acc1)
+        return
+    check(rc, 'gemm_h2_pair')
+    timed_end(gemm_profile, e0, M, N0 + N1, A.cols, 'kk/h2/pipe4')
+
+
 # ---- Dense -> LayerNorm (-> SiLU) in one launch (genrl_gemm_h2_ln: the column tiles of a row block exchange their row statistics inside ONE
 # XCD's L2 behind a barrier of N / 64 workgroups, csrc/gemm_planes.hip LnEpi).  Two such launches must never run concurrently (each would wait
 # for workgroups the other keeps off the CUs), so the fused form is taken on the iteration's MAIN stream only -- never on a side stream of

@@ -84,6 +84,16 @@ int genrl_gemm_h2(const uint16_t* a0, long a0_ld, long a0_plane, const float* a0
                   const float* b0_inv, int k0, const uint16_t* a1, long a1_ld, long a1_plane, const float* a1_inv,
                   const uint16_t* b1, long b1_ld, long b1_plane, const float* b1_inv, int k1,
                   float* C, long ldc, const float* bias, int M, int N, int accumulate, void* stream);
+/* Two one-segment products on ONE A operand in one launch: C0 (+)= A B0^T (M x N0) and C1 (+)= A B1^T (M x N1), no bias (the two dgrads of
+ * one gradient: the imagination rollout's GRU backward).  Column tile t < N0 / 64 of the launch belongs to product 0, the rest to product 1;
+ * each tile runs genrl_gemm_h2's 64x64 tile body on its own product's (B, C, ldc, accumulate): each C is bitwise what its own genrl_gemm_h2
+ * launch gives.  The tile order places both products' tiles of a row panel on the same XCDs, so that A is fetched once per XCD.
+ * GENRL_EINVAL -- the caller launches the two products itself -- unless N0 % 64 == 0 and genrl_gemm_h2 would run both products on the
+ * three-stage 64x64 instantiation (fewer than 2048 tiles each; not 257+ tiles with k <= 1536). */
+int genrl_gemm_h2_pair(const uint16_t* a, long a_ld, long a_plane, const float* a_inv, int k,
+                       const uint16_t* b0, long b0_ld, long b0_plane, const float* b0_inv, float* C0, long ldc0, int N0, int accumulate0,
+                       const uint16_t* b1, long b1_ld, long b1_plane, const float* b1_inv, float* C1, long ldc1, int N1, int accumulate1,
+                       int M, void* stream);
 /* genrl_gemm_h2 (one segment) whose output rows are the logits of N / 32 categorical latents of 32 classes (the RSSM prior head
  * inside the imagination rollout, agent/dreamer_utils.py:466-470,177-197): the same launch also takes the unimix softmax +
  * exponential-race sample of every latent (argmax_k pn_k / q_k, first maximum wins) from the logits it has just formed and
@@ -226,17 +236,21 @@ typedef struct {
   const float* dist_b;
   genrl_planes_ref pw0s, pw0d;                                                /* policy layer 0: the stoch / deter column blocks of its weight */
   genrl_planes_ref pw[8]; const float* pb[8]; const float* pg[8]; const float* pbe[8]; float peps[8]; int pU[8];
-  float* ppre[8]; float* py[8]; float* pmean[8]; float* prstd[8]; genrl_planes_ref pyp[8];
+  float* ppre[8]; float* py[8]; float* pmean[8]; float* prstd[8]; genrl_planes_ref pyp[8];    /* py[l], l < L - 1, may be NULL: planes only */
   const float* head_w; const float* head_b;
   /* round 6: Dense -> LayerNorm in ONE launch (genrl_gemm_h2_ln) for the policy layers, img_in and img_out where genrl_gemm_h2_ln_ok(N, width):
    * 10 launches per step instead of 16.  ln_sync == NULL: the 16-launch form.  ln_part / ln_sync: genrl_gemm_h2_ln's workspaces. */
   float* ln_part; unsigned* ln_sync;
 } genrl_rollout;
 int genrl_imagine_seq_fwd(const genrl_rollout* r, void* stream);
-/* ... and its backward through the frozen dynamics (the dgrad chain of _RolloutPlanes.backward, 10 launches per step, same order): ds / dd
+/* ... and its backward through the frozen dynamics (the dgrad chain of _RolloutPlanes.backward, same order; 8 launches per step + 1: the two
+ * GRU dgrads are one genrl_gemm_h2_pair launch, and with dx_pre_all the head's backward runs once behind the loop): ds / dd
  * (H+1,N,S K) / (H+1,N,D) hold the upstream state gradients on entry and the complete ones on return; dl_in: upstream logit gradients
  * (H+1,N,S K) or NULL; dact_all: upstream action gradients in padded rows (H+1,N,AP) or NULL; d_raw (H,N,2A): the policy output's
- * gradient per step (handed to the policy's batched backward).  Scratch: dlg, dov, do_pre, dg_pre, dx, dx_pre + their planes, dha / dhb. */
+ * gradient per step (handed to the policy's batched backward).  Scratch: dlg, dov, do_pre, dx, dx_pre + their planes, dha / dhb.  What only plane
+ * products read is written as planes only: dg_pre is never written (may be NULL), dlg only with dl_in (the accumulating form) or where the
+ * one-hot backward cannot write planes itself, do_pre may be NULL (genrl_ln_act_bwd_h2).  dx_pre_all (H,N,U) or NULL: a slab per step for
+ * d x_pre -- genrl_actor_head_linear_bwd then runs ONCE over all H N rows behind the loop instead of once per step on dx_pre (N,U). */
 typedef struct {
   int H, N, S, K, D, A, AP, U;
   float unimix, min_std, max_std;
@@ -248,6 +262,7 @@ typedef struct {
   genrl_planes_ref wt_dist, wt_out, wt_g_x, wt_g_h, wt_in_s;
   const float* waT;
   const float* out_g; const float* out_be; const float* gru_g; const float* gru_be; const float* in_g; const float* in_be;
+  float* dx_pre_all;
 } genrl_rollout_bwd;
 int genrl_imagine_seq_bwd(const genrl_rollout_bwd* r, void* stream);
 /* The same two loops for the fp32-OPERAND rollout (genrl_amd/ops.py::_Rollout: fewer than GENRL_PLANES_MIN_ROWS rows -- the per-GPU sizes
@@ -394,6 +409,7 @@ int genrl_ln_act_bwd_h2(const float* dy, long lddy, const float* x, long ldx, co
 int genrl_gru_gates_fwd_h2(const float* pre, const float* h, long ldh, const float* gamma, const float* beta,
                            float* hout, long ldo, float* hout2, const float* hout2_scale, float* mean, float* rstd,
                            int R, int D, float eps, uint16_t* hp, long ldp, long plane, float* inv, void* stream);
+/* (dpre may be NULL when dprep is given: the pre-activation gradient as planes only; NULL without planes: GENRL_EINVAL) */
 int genrl_gru_gates_bwd_h2(const float* dhout, long lddo, const float* dhout2, const float* dhout2_scale,
                            const float* pre, const float* h, long ldh, const float* gamma, const float* beta,
                            const float* mean, const float* rstd, float* dpre, float* dh, long lddh, float* dgamma,
@@ -405,6 +421,9 @@ int genrl_actor_head_fwd_h2(const float* raw, const float* eps, float* action, f
 /* planes of the sample / of d logits: rows of `rowlen` = S*K elements (the sample's scale is the constant 2^14) */
 int genrl_onehot_fwd_h2(const float* logits, const float* q, float* sample, float* probs, long G, int K, float unimix,
                         uint16_t* sp, int rowlen, long ldp, long plane, float* inv, void* stream);
+/* dlogits may be NULL (planes only) when accumulate == 0 and the kernel writes the planes itself -- genrl_onehot_bwd_planes_only_ok(K, rowlen):
+ * K in {4, 8, 16, 32, 64}, rowlen % 64 == 0, rowlen <= 1024; GENRL_EINVAL otherwise */
+int genrl_onehot_bwd_planes_only_ok(int K, int rowlen);
 int genrl_onehot_bwd_h2(const float* logits, const float* gsample, float* dlogits, long G, int K, float unimix,
                         int accumulate, uint16_t* dp, int rowlen, long ldp, long plane, float* inv, void* stream);
 
