@@ -6,7 +6,7 @@ import ctypes
 import torch
 from torch.autograd import Function
 
-from ._lib import lib, check, GenrlHipError
+from ._lib import lib, check, GenrlHipError, struct as _cstruct
 
 UNIMIX = 0.99
 gemm_profile = None      # set to a list to record (M, N, K, start_event, end_event) per sgemm launch
@@ -23,6 +23,44 @@ def _p(t):
         raise GenrlHipError('genrl_amd ops need tensors on the MI355X (no CPU fallback)')
     assert t.is_contiguous(), 'non-contiguous tensor handed to a HIP op'
     return t.data_ptr()
+
+
+# ---- the argument structs of the C launch loops (csrc/seq.hip, the batched split / reduction): their classes come from the header
+# (_lib.struct; a name that is no field raises on assignment) and fill() converts what goes into them by the fields' declared types
+_PREF = _cstruct('genrl_planes_ref')
+_kinds = {}              # struct class -> {field name: 0 scalar | 1 pointer | 2 genrl_planes_ref} (of the element, for an array field)
+
+
+def _field_kinds(cls):
+    elem = lambda ct: getattr(ct, '_type_', ct) if issubclass(ct, ctypes.Array) else ct
+    _kinds[cls] = {n: 1 if elem(ct) is ctypes.c_void_p else 2 if elem(ct) is _PREF else 0 for n, ct in cls._fields_}
+    return _kinds[cls]
+
+
+def fill(a, at=None, **fields):
+    """set fields of the argument struct a by name and return it; a name the struct does not have raises.  Values go in by the field's
+    declared type: a pointer takes a tensor (through _p: the same refusals as every launch), None or an address that was already offset;
+    a genrl_planes_ref takes a planes.Planes handle; a scalar goes in as it is.  at: element `at` of array fields instead (the per-layer
+    arrays of the rollouts)."""
+    kinds = _kinds.get(type(a)) or _field_kinds(type(a))
+    for n, v in fields.items():
+        k = kinds.get(n)
+        if k is None:
+            raise AttributeError(f'{type(a).__name__} has no field {n!r}')
+        if k == 2:
+            v = _PREF(v.t.data_ptr(), v.ld, v.plane, v.inv.data_ptr())
+        elif k == 1 and v is not None and v.__class__ is not int:
+            v = _p(v)
+        if at is None:
+            setattr(a, n, v)
+        else:
+            getattr(a, n)[at] = v
+    return a
+
+
+def _max_layers(name):
+    """how many policy layers the struct `name` has room for (the length of its per-layer arrays)"""
+    return dict(_cstruct(name)._fields_)['pw']._length_
 
 
 def _on_gpu(*ts):
@@ -102,11 +140,6 @@ def defer_reduce(M, N, ws, g0, g1, g2=None):
     return 4
 
 
-class _ReduceDesc(ctypes.Structure):          # genrl_reduce_desc (include/genrl_hip.h)
-    _fields_ = [('part', ctypes.c_void_p), ('out0', ctypes.c_void_p), ('out1', ctypes.c_void_p), ('out2', ctypes.c_void_p),
-                ('nchunk', ctypes.c_int), ('N', ctypes.c_int), ('np', ctypes.c_int), ('accumulate', ctypes.c_int)]
-
-
 def defer_flush():
     """sum every partial set registered since defer_begin into its gradient buffers (on the current stream) and stop deferring"""
     global _deferred
@@ -129,8 +162,10 @@ def defer_flush():
     for _, its in rounds:
         for it in its:                 # a workspace filled on a side stream (the connector's) and summed here: keep it alive for this stream
             it[0].record_stream(cur)
-        arr = (_ReduceDesc * len(its))()
+        arr = (_cstruct('genrl_reduce_desc') * len(its))()
         for d, (ws, parts, N, np_, g0, g1, g2) in zip(arr, its):
+            # (addresses and scalars, one descriptor per partial set: assigned directly, several times cheaper than fill(); a name that is
+            # no field raises all the same, _lib)
             d.part, d.out0, d.out1, d.out2 = ws.data_ptr(), g0.data_ptr(), g1.data_ptr(), (g2.data_ptr() if g2 is not None else None)
             d.nchunk, d.N, d.np, d.accumulate = parts, N, np_, 1
         check(lib().genrl_reduce_params_batch(arr, len(its), _stream()), 'reduce_params_batch')
@@ -1009,45 +1044,93 @@ def trunc_normal_mean_std(raw, min_std=0.1, init_std=0.0):
     return _actor_mean_std(raw, _TRUNC_HEAD, min_std, init_std)
 
 
-# ---- genrl_rollout_f32 (include/genrl_hip.h): the arguments of the fp32-operand rollout's launch loops in C (csrc/seq.hip)
-_FP, _CF, _CI = ctypes.c_void_p, ctypes.c_float, ctypes.c_int
+# ---- the imagination rollout's autograd node, the part its two operand kinds share (_Rollout below: fp32 matrices, genrl_rollout_f32;
+# ops_planes._RolloutPlanes: h2 planes, genrl_rollout / genrl_rollout_bwd)
+
+def _rollout_buffers(stoch0, deter0, logit0, eps, q, sp, tape):
+    """the forward's time-major buffers with the initial state in row block 0 -> dims (H, N, S, K, D, A, U, AP), bufs (stoch, deter,
+    logit, action, raws, x_pre, g_pre, o_pre, st), eps, q (contiguous).  Actions live in rows of AP = A rounded up to 4 floats (zero
+    padded): the thin products of a step (x += action W_a^T, d action = dx W_a) then meet the vector-load preconditions of the GEMM."""
+    H, N, S, K = tape.H, tape.N, sp.S, sp.K
+    SK, D, A, U = S * K, deter0.shape[1], eps.shape[-1], sp.in_w.shape[0]
+    dev = deter0.device
+    f = lambda *shape: torch.empty(*shape, device=dev)
+    AP = (A + 3) // 4 * 4
+    stoch = f(H + 1, N, SK); deter = f(H + 1, N, D); logit = f(H + 1, N, SK)
+    action = torch.zeros(H + 1, N, AP, device=dev)
+    raws = f(H, N, 2 * A)
+    stoch[0].copy_(stoch0.reshape(N, SK)); deter[0].copy_(deter0); logit[0].copy_(logit0.reshape(N, SK))
+    x_pre, g_pre, o_pre = f(H, N, U), f(H, N, 3 * D), f(H, N, U)
+    st = {k: f(H, N) for k in ('xm', 'xr', 'gm', 'gr', 'om', 'or')}
+    return (H, N, S, K, D, A, U, AP), (stoch, deter, logit, action, raws, x_pre, g_pre, o_pre, st), _f32(eps).contiguous(), _f32(q).contiguous()
 
 
-class _RolloutF32Args(ctypes.Structure):
-    _fields_ = ([(n, _CI) for n in ('H', 'N', 'S', 'K', 'D', 'A', 'AP', 'U', 'L')] + [(n, _CF) for n in ('unimix', 'min_std', 'max_std')]
-                + [(n, _FP) for n in ('stoch', 'deter', 'logit', 'action', 'raws', 'eps', 'q', 'x_pre', 'x', 'g_pre', 'o_pre', 'o',
-                                      'xm', 'xr', 'gm', 'gr', 'om', 'orr', 'ws_in', 'wa', 'gru_w', 'out_w', 'dist_w')]
-                + [('in_b', _FP), ('in_g', _FP), ('in_be', _FP), ('in_eps', _CF), ('gru_g', _FP), ('gru_be', _FP),
-                   ('out_b', _FP), ('out_g', _FP), ('out_be', _FP), ('out_eps', _CF), ('dist_b', _FP),
-                   ('pw', _FP * 8), ('pb', _FP * 8), ('pg', _FP * 8), ('pbe', _FP * 8), ('peps', _CF * 8), ('pU', _CI * 8),
-                   ('ppre', _FP * 8), ('py', _FP * 8), ('pmean', _FP * 8), ('prstd', _FP * 8), ('head_w', _FP), ('head_b', _FP),
-                   ('ws', _FP), ('ws_floats', ctypes.c_long)]
-                + [(n, _FP) for n in ('ds', 'dd', 'dl_in', 'dact_all', 'd_raw', 'dlg', 'dov', 'do_pre', 'dg_pre', 'dx', 'dx_pre', 'dha', 'dhb', 'waT')])
-
-
-def _rollout_f32_args(sp, tape, dims, bufs, ws_in, wa, x=None, o=None, eps=None, q=None):
-    """the fields both directions share; -> (args, the workspace tensor that must outlive the call)"""
+def _rollout_fields(sp, tape, dims, bufs, x=None, o=None, eps=None, q=None):
+    """the fields genrl_rollout and genrl_rollout_f32 have in common (genrl_rollout_bwd: a subset of them) -> {name: value} for fill(),
+    [{name: value} per policy layer] for fill(at=)"""
     H, N, S, K, D, A, U, AP = dims
     stoch, deter, logit, action, raws, x_pre, g_pre, o_pre, st = bufs
-    a = _RolloutF32Args()
-    a.H, a.N, a.S, a.K, a.D, a.A, a.AP, a.U, a.L = H, N, S, K, D, A, AP, U, len(tape.layers)
-    a.unimix, a.min_std, a.max_std = UNIMIX, sp.min_std, sp.max_std
-    for n_, t_ in (('stoch', stoch), ('deter', deter), ('logit', logit), ('action', action), ('raws', raws), ('eps', eps), ('q', q), ('x_pre', x_pre),
-                   ('x', x), ('g_pre', g_pre), ('o_pre', o_pre), ('o', o), ('xm', st['xm']), ('xr', st['xr']), ('gm', st['gm']), ('gr', st['gr']),
-                   ('om', st['om']), ('orr', st['or']), ('ws_in', ws_in), ('wa', wa), ('gru_w', sp.gru_w), ('out_w', sp.out_w), ('dist_w', sp.dist_w),
-                   ('in_b', sp.in_b), ('in_g', sp.in_g), ('in_be', sp.in_be), ('gru_g', sp.gru_g), ('gru_be', sp.gru_be), ('out_b', sp.out_b),
-                   ('out_g', sp.out_g), ('out_be', sp.out_be), ('dist_b', sp.dist_b), ('head_w', tape.head_w), ('head_b', tape.head_b)):
-        setattr(a, n_, _p(t_))
-    a.in_eps, a.out_eps = sp.in_eps, sp.out_eps
-    for l, (W_, b_, ga_, be_, eps_) in enumerate(tape.layers):
-        a.pw[l], a.pb[l], a.pg[l], a.pbe[l], a.peps[l], a.pU[l] = _p(W_), _p(b_), _p(ga_), _p(be_), eps_, W_.shape[0]
-        a.ppre[l], a.py[l], a.pmean[l], a.prstd[l] = _p(tape.pre[l]), _p(tape.y[l]), _p(tape.mean[l]), _p(tape.rstd[l])
+    common = dict(H=H, N=N, S=S, K=K, D=D, A=A, AP=AP, U=U, L=len(tape.layers), unimix=UNIMIX, min_std=sp.min_std, max_std=sp.max_std,
+                  stoch=stoch, deter=deter, logit=logit, action=action, raws=raws, eps=eps, q=q, x_pre=x_pre, x=x, g_pre=g_pre, o_pre=o_pre, o=o,
+                  xm=st['xm'], xr=st['xr'], gm=st['gm'], gr=st['gr'], om=st['om'], orr=st['or'],
+                  in_b=sp.in_b, in_g=sp.in_g, in_be=sp.in_be, in_eps=sp.in_eps, gru_g=sp.gru_g, gru_be=sp.gru_be,
+                  out_b=sp.out_b, out_g=sp.out_g, out_be=sp.out_be, out_eps=sp.out_eps, dist_b=sp.dist_b, head_w=tape.head_w, head_b=tape.head_b)
+    layers = [dict(pb=b_, pg=ga_, pbe=be_, peps=eps_, pU=W_.shape[0], ppre=tape.pre[l], py=tape.y[l], pmean=tape.mean[l], prstd=tape.rstd[l])
+              for l, (W_, b_, ga_, be_, eps_) in enumerate(tape.layers)]
+    return common, layers
+
+
+def _rollout_outputs(ctx, sp, dims, bufs, eps, *keep):
+    """what the forward leaves for the backward (ctx.bufs = stoch, deter, logit, raws, eps, x_pre, g_pre, o_pre, st, *keep) -> its outputs"""
+    H, N, S, K, D, A, U, AP = dims
+    stoch, deter, logit, action, raws, x_pre, g_pre, o_pre, st = bufs
+    sp.tape.inputs = (stoch, deter)
+    ctx.sp = sp
+    ctx.bufs = (stoch, deter, logit, raws, eps, x_pre, g_pre, o_pre, st, *keep)
+    ctx.dims = dims
+    # (views, never the buffers themselves: ctx.bufs holds `deter` and `raws`, and an OUTPUT tensor kept on ctx is a reference cycle
+    # through its grad_fn that Python's collector cannot see -- every eager iteration's rollout buffers, 1.4 GiB, stayed alive)
+    return stoch.reshape(H + 1, N, S, K), deter.view(H + 1, N, D), logit.reshape(H + 1, N, S, K), action[:, :, :A], raws.view(H, N, 2 * A)
+
+
+def _rollout_upstream(dims, dev, d_stoch, d_deter, d_logit, d_action):
+    """the backward's gradient buffers -> ds, dd (the upstream state gradients, cloned: the loop completes them in place), dl_in (upstream
+    logit gradients or None), dact_all (upstream action gradients in rows padded like the forward's actions, or None), dha, dhb (ping-pong:
+    the recurrent gradient into deter_h from step h's GRU)"""
+    H, N, S, K, D, A, U, AP = dims
+    SK = S * K
+    ds = d_stoch.reshape(H + 1, N, SK).clone() if d_stoch is not None else torch.zeros(H + 1, N, SK, device=dev)
+    dd = d_deter.clone() if d_deter is not None else torch.zeros(H + 1, N, D, device=dev)
+    dl_in = d_logit.reshape(H + 1, N, SK).contiguous() if d_logit is not None else None
+    dact_all = None
+    if d_action is not None:
+        dact_all = torch.zeros(H + 1, N, AP, device=dev)
+        dact_all[:, :, :A].copy_(d_action.contiguous())
+    return ds, dd, dl_in, dact_all, torch.empty(N, D, device=dev), torch.empty(N, D, device=dev)
+
+
+def _rollout_param_grads(tape, d_raws):
+    """the backward's tail: the policy's batched backward over all H N rows -> the node's gradients (none for the states, noise and spec)"""
+    if d_raws is not None:
+        tape.d_raw += d_raws
+    dWh, dbh, grads = tape._backward()
+    return (None, None, None, None, None, None, dWh, dbh, *[g for lg in grads for g in lg])
+
+
+def _rollout_f32_args(sp, tape, dims, bufs, ws_in, wa, x=None, o=None, eps=None, q=None, **bwd):
+    """genrl_rollout_f32: the common fields, the weights as fp32 matrices, the split-K workspace and the backward's own fields (bwd);
+    -> (args, the workspace tensor that must outlive the call)"""
+    H, N, S, K, D, A, U, AP = dims
+    common, layers = _rollout_fields(sp, tape, dims, bufs, x, o, eps, q)
     SK = S * K
     shapes = [(N, U, SK), (N, U, D), (N, U, U), (N, U, AP), (N, 3 * D, U), (N, 3 * D, D), (N, SK, U), (N, D, U), (N, D, 3 * D), (N, U, 3 * D)]
     shapes += [(N, l_[0].shape[0], l_[0].shape[0]) for l_ in tape.layers]
     nws = max(lib().genrl_sgemm_ws_floats(*s_) for s_ in shapes)
-    ws = torch.empty(max(nws, 1), device=deter.device)
-    a.ws, a.ws_floats = ws.data_ptr(), nws
+    ws = torch.empty(max(nws, 1), device=bufs[1].device)
+    a = fill(_cstruct('genrl_rollout_f32')(), **common, ws_in=ws_in, wa=wa, gru_w=sp.gru_w, out_w=sp.out_w, dist_w=sp.dist_w,
+             ws=ws.data_ptr(), ws_floats=nws, **bwd)
+    for l, fields in enumerate(layers):
+        fill(a, at=l, pw=tape.layers[l][0], **fields)
     return a, ws
 
 
@@ -1243,36 +1326,23 @@ class _Rollout(Function):
     def forward(ctx, stoch0, deter0, logit0, eps, q, spec, head_w, head_b, *actor_params):
         ctx.set_materialize_grads(False)
         sp, tape = spec, spec.tape
-        H, N = tape.H, tape.N
-        S, K = sp.S, sp.K
-        SK, D = S * K, deter0.shape[1]
-        A = eps.shape[-1]
-        U = sp.in_w.shape[0]
         dev = deter0.device
-        f = lambda *shape: torch.empty(*shape, device=dev)
-        # actions live in rows of AP = A rounded up to 4 floats (zero padded) and the action slice of the input
-        # layer's weight is copied once into a (U, AP) zero-padded matrix: both thin products of a step
-        # (x += action W_a^T, d action = dx W_a) then meet the vector-load preconditions of the GEMM
-        AP = (A + 3) // 4 * 4
-        stoch = f(H + 1, N, SK); deter = f(H + 1, N, D); logit = f(H + 1, N, SK); action = torch.zeros(H + 1, N, AP, device=dev)
-        wa = torch.zeros(sp.in_w.shape[0], AP, device=dev)
+        A, SK = eps.shape[-1], sp.S * sp.K
+        # the action slice of the input layer's weight is copied once into a (U, AP) zero-padded matrix (_rollout_buffers: why)
+        wa = torch.zeros(sp.in_w.shape[0], (A + 3) // 4 * 4, device=dev)
         wa[:, :A].copy_(sp.in_w[:, SK:SK + A])
         ws_in = sp.in_w[:, :SK].contiguous()     # stoch slice with 16-byte aligned rows (the (U, SK + A) weight's are not)
-        raws = f(H, N, 2 * A)
-        stoch[0].copy_(stoch0.reshape(N, SK)); deter[0].copy_(deter0); logit[0].copy_(logit0.reshape(N, SK))
-        x_pre, x = f(H, N, U), f(H, N, U)
-        g_pre = f(H, N, 3 * D)
-        o_pre, o = f(H, N, U), f(H, N, U)
-        st = {k: f(H, N) for k in ('xm', 'xr', 'gm', 'gr', 'om', 'or')}
-        eps = _f32(eps).contiguous(); q = _f32(q).contiguous()
+        dims, bufs, eps, q = _rollout_buffers(stoch0, deter0, logit0, eps, q, sp, tape)
+        H, N, S, K, D, A, U, AP = dims
+        stoch, deter, logit, action, raws, x_pre, g_pre, o_pre, st = bufs
+        x, o = torch.empty(H, N, U, device=dev), torch.empty(H, N, U, device=dev)
         Kin, Kg = sp.in_w.shape[1], sp.gru_w.shape[1]
         pt = lambda t, off: t.data_ptr() + 4 * off
-        seq_c = SEQ_C and gemm_profile is None and len(tape.layers) <= 8
+        seq_c = SEQ_C and gemm_profile is None and len(tape.layers) <= _max_layers('genrl_rollout_f32')
         if seq_c:
             # the H-step launch loop in C (csrc/seq.hip: genrl_imagine_seq_f32_fwd -- the loop below, launch for launch)
-            a, ws_keep = _rollout_f32_args(sp, tape, (H, N, S, K, D, A, U, AP), (stoch, deter, logit, action, raws, x_pre, g_pre, o_pre, st),
-                                           ws_in, wa, x=x, o=o, eps=eps, q=q)
-            check(lib().genrl_imagine_seq_f32_fwd(ctypes.addressof(a), _stream()), 'imagine_seq_f32_fwd')
+            a, ws_keep = _rollout_f32_args(sp, tape, dims, bufs, ws_in, wa, x=x, o=o, eps=eps, q=q)
+            check(lib().genrl_imagine_seq_f32_fwd(a, _stream()), 'imagine_seq_f32_fwd')
         for h in (() if seq_c else range(H)):
             sN, dN = h * N * SK, h * N * D
             tape._forward(h, stoch[h], deter[h], head=False)
@@ -1295,47 +1365,28 @@ class _Rollout(Function):
             sgemm(o, U, 1, sp.dist_w, U, 1, logit, SK, sp.dist_b, N, SK, U, a_off=h * N * U, c_off=sN + N * SK)
             check(lib().genrl_onehot_fwd(pt(logit, sN + N * SK), pt(q, h * N * SK), pt(stoch, sN + N * SK), None, N * S, K,
                                          UNIMIX, _stream()), 'onehot_fwd')
-        tape.inputs = (stoch, deter)
-        ctx.sp = sp
-        ctx.bufs = (stoch, deter, logit, raws, eps, x_pre, g_pre, o_pre, st, wa, ws_in)
-        ctx.nparams = len(actor_params)
-        ctx.dims = (H, N, S, K, D, A, U)
-        # (views, never the buffers themselves: ctx.bufs holds `deter` and `raws`, and an OUTPUT tensor kept on ctx is a reference cycle
-        # through its grad_fn that Python's collector cannot see -- every eager iteration's rollout buffers, 1.4 GiB, stayed alive)
-        return stoch.reshape(H + 1, N, S, K), deter.view(H + 1, N, D), logit.reshape(H + 1, N, S, K), action[:, :, :A], raws.view(H, N, 2 * A)
+        return _rollout_outputs(ctx, sp, dims, bufs, eps, wa, ws_in)
 
     @staticmethod
     def backward(ctx, d_stoch, d_deter, d_logit, d_action, d_raws):
         sp, tape = ctx.sp, ctx.sp.tape
         stoch, deter, logit, raws, eps, x_pre, g_pre, o_pre, st, wa, ws_in = ctx.bufs
-        H, N, S, K, D, A, U = ctx.dims
+        H, N, S, K, D, A, U, AP = ctx.dims
         SK = S * K
         dev = deter.device
-        z = lambda *shape: torch.zeros(*shape, device=dev)
-        ds = d_stoch.reshape(H + 1, N, SK).clone() if d_stoch is not None else z(H + 1, N, SK)
-        dd = d_deter.clone() if d_deter is not None else z(H + 1, N, D)
-        dl_in = d_logit.reshape(H + 1, N, SK).contiguous() if d_logit is not None else None
-        da_in = d_action.contiguous() if d_action is not None else None
+        ds, dd, dl_in, dact_all, dha, dhb = _rollout_upstream(ctx.dims, dev, d_stoch, d_deter, d_logit, d_action)
         Kin, Kg = sp.in_w.shape[1], sp.gru_w.shape[1]
         f = lambda *shape: torch.empty(*shape, device=dev)
-        AP = wa.shape[1]
         dlg, do, do_pre, dg_pre, dx, dx_pre = f(N, SK), f(N, U), f(N, U), f(N, 3 * D), f(N, U), f(N, U)
         waT = wa[:, :A].t().contiguous()                  # (A, U): the action columns, for the fused head backward
-        dha, dhb = f(N, D), f(N, D)
-        cur, nxt = dha, None                              # ping-pong: recurrent gradient into deter_h from step h's GRU
+        cur, nxt = dha, None
         pt = lambda t, off: t.data_ptr() + 4 * off
-        dact_all = None
-        if da_in is not None:                 # upstream action gradients, once, in rows padded like the forward's actions
-            dact_all = torch.zeros(H + 1, N, AP, device=dev)
-            dact_all[:, :, :A].copy_(da_in)
-        seq_c = SEQ_C and gemm_profile is None and len(tape.layers) <= 8
+        seq_c = SEQ_C and gemm_profile is None and len(tape.layers) <= _max_layers('genrl_rollout_f32')
         if seq_c:
-            a, ws_keep = _rollout_f32_args(sp, tape, (H, N, S, K, D, A, U, AP), (None, deter, logit, None, raws, x_pre, g_pre, o_pre, st),
-                                           ws_in, wa, eps=eps)
-            for n_, t_ in (('ds', ds), ('dd', dd), ('dl_in', dl_in), ('dact_all', dact_all), ('d_raw', tape.d_raw), ('dlg', dlg), ('dov', do),
-                           ('do_pre', do_pre), ('dg_pre', dg_pre), ('dx', dx), ('dx_pre', dx_pre), ('dha', dha), ('dhb', dhb), ('waT', waT)):
-                setattr(a, n_, _p(t_))
-            check(lib().genrl_imagine_seq_f32_bwd(ctypes.addressof(a), _stream()), 'imagine_seq_f32_bwd')
+            a, ws_keep = _rollout_f32_args(sp, tape, ctx.dims, (None, deter, logit, None, raws, x_pre, g_pre, o_pre, st), ws_in, wa, eps=eps,
+                                           ds=ds, dd=dd, dl_in=dl_in, dact_all=dact_all, d_raw=tape.d_raw, dlg=dlg, dov=do, do_pre=do_pre,
+                                           dg_pre=dg_pre, dx=dx, dx_pre=dx_pre, dha=dha, dhb=dhb, waT=waT)
+            check(lib().genrl_imagine_seq_f32_bwd(a, _stream()), 'imagine_seq_f32_bwd')
         for h in (() if seq_c else range(H - 1, -1, -1)):
             sN, dN = h * N * SK, h * N * D
             # grad wrt stoch_{h+1} (complete in ds[h+1]) -> logits (straight-through), plus any direct logit gradient
@@ -1360,11 +1411,7 @@ class _Rollout(Function):
                                                     AP, pt(raws, h * N * 2 * A), pt(eps, h * N * A), pt(tape.d_raw, h * N * 2 * A), N, U, A,
                                                     sp.min_std, sp.max_std, _stream()), 'actor_head_linear_bwd')
             nxt, cur = cur, (dhb if cur is dha else dha)
-        if d_raws is not None:
-            tape.d_raw += d_raws
-        dWh, dbh, grads = tape._backward()
-        flat = [g for lg in grads for g in lg]
-        return (None, None, None, None, None, None, dWh, dbh, *flat)
+        return _rollout_param_grads(tape, d_raws)
 
 
 def imagine_rollout(stoch0, deter0, logit0, eps, q, spec):
@@ -1993,25 +2040,11 @@ def dense_ln_act(x1, x2, W, b, gamma, beta, eps=1e-5):
 
 # ------------------------------------------------------------------ RSSM observe scan with the posterior inside the recurrence
 
-class _ObserveArgs(ctypes.Structure):          # genrl_observe (include/genrl_hip.h)
-    _fields_ = ([(n, _CI) for n in ('T', 'B', 'S', 'K', 'D', 'U')] + [(n, _CF) for n in ('unimix', 'in_eps', 'out_eps')]
-                + [('w_in_s', _FP), ('ld_in_s', ctypes.c_long), ('w_g', _FP), ('ld_g', ctypes.c_long), ('w_o', _FP),
-                   ('ld_o', ctypes.c_long), ('w_d', _FP)]
-                + [(n, _FP) for n in ('in_g', 'in_be', 'gru_g', 'gru_be', 'out_g', 'out_be', 'dist_b', 'mask', 'q')]
-                + [('out_b', _FP), ('opre_acc', _CI), ('idx', _FP), ('w_in_sT', _FP), ('fuse_sample', _CI)]
-                + [(n, _FP) for n in ('sm', 'xpre', 'xh', 'gpre', 'deter', 'opre', 'o', 'plog', 'pst',
-                                      'xm', 'xr', 'gm', 'gr', 'om', 'orr', 'ws')]
-                + [('ws_floats', ctypes.c_long)]
-                + [(n, _FP) for n in ('d_pst', 'dlg', 'dd', 'dov', 'dopre', 'dgpre', 'dxh', 'dxpre', 'dsa', 'dsb', 'dhd_a', 'dhd_b',
-                                      'dgamma', 'dbeta', 'gws')]
-                + [('direct', _CI)])
-
-
 def _observe_args(dims, eps, W_in, W_g, W_o, W_d, params, bufs, stats, **extra):
-    """the _ObserveArgs that _ObserveSeq's forward and backward and rssm_imagine_seq share -> (args, w_s, ws): the latent block of W_in
+    """the genrl_observe (include/genrl_hip.h) that _ObserveSeq's forward and backward and rssm_imagine_seq share -> (args, w_s, ws): the latent block of W_in
     the scan reads and its GEMM workspace, both to be kept alive over the call.  W_in: the (U, S K + A) weight, or the w_s of an earlier
     call; params = (in_g, in_be, gru_g, gru_be, out_g, out_be, dist_b), bufs = (sm, xpre, xh, gpre, deter, opre, o, plog), stats (6, T, B);
-    extra: the pointer fields that differ (mask, q, pst, out_b, the backward's own).  opre_acc and the ping-pong pairs are the caller's."""
+    extra: the fields that differ (opre_acc, mask, q, pst, out_b, the backward's own)."""
     T, B, S, K, D, U = dims
     SK, Kin = S * K, W_in.shape[1]
     if Kin % 4:          # the latent block of _img_in, rows 16-byte aligned (SK + A is not a multiple of 4 with 6 or 10 actions)
@@ -2019,18 +2052,13 @@ def _observe_args(dims, eps, W_in, W_g, W_o, W_d, params, bufs, stats, **extra):
         copy2d(W_in, Kin, w_s, SK, U, SK)
     else:
         w_s = W_in
-    a = _ObserveArgs()
-    a.T, a.B, a.S, a.K, a.D, a.U = dims
-    a.unimix, a.in_eps, a.out_eps = UNIMIX, eps[0], eps[1]
-    a.w_in_s, a.ld_in_s, a.w_g, a.ld_g, a.w_o, a.ld_o, a.w_d = _p(w_s), w_s.shape[1], _p(W_g), U + D, _p(W_o), W_o.shape[1], _p(W_d)
-    names = ('in_g', 'in_be', 'gru_g', 'gru_be', 'out_g', 'out_be', 'dist_b', 'sm', 'xpre', 'xh', 'gpre', 'deter', 'opre', 'o', 'plog')
-    for n_, t_ in (*zip(names, (*params, *bufs)), *extra.items()):
-        setattr(a, n_, _p(t_))
-    for i, n_ in enumerate(('xm', 'xr', 'gm', 'gr', 'om', 'orr')):
-        setattr(a, n_, stats[i].data_ptr())
+    names = ('in_g', 'in_be', 'gru_g', 'gru_be', 'out_g', 'out_be', 'dist_b', 'sm', 'xpre', 'xh', 'gpre', 'deter', 'opre', 'o', 'plog',
+             'xm', 'xr', 'gm', 'gr', 'om', 'orr')
     nws = max(lib().genrl_sgemm_ws_floats(*s_) for s_ in _observe_shapes(B, SK, U, D))
     ws = torch.empty(max(nws, 1), device=W_in.device)
-    a.ws, a.ws_floats = ws.data_ptr(), nws
+    a = fill(_cstruct('genrl_observe')(), T=T, B=B, S=S, K=K, D=D, U=U, unimix=UNIMIX, in_eps=eps[0], out_eps=eps[1],
+             w_in_s=w_s, ld_in_s=w_s.shape[1], w_g=W_g, ld_g=U + D, w_o=W_o, ld_o=W_o.shape[1], w_d=W_d,
+             **dict(zip(names, (*params, *bufs, *stats))), ws=ws.data_ptr(), ws_floats=nws, **extra)
     return a, w_s, ws
 
 
@@ -2043,7 +2071,7 @@ def _sgemm_ptr(A, a_rs, a_ks, B, b_rs, b_ks, C, ldc, bias, M, N, K, acc, ws, nws
 
 
 def _observe_fwd_py(a):
-    """csrc/seq.hip::genrl_observe_seq_fwd, launch for launch (a: _ObserveArgs)"""
+    """csrc/seq.hip::genrl_observe_seq_fwd, launch for launch (a: genrl_observe)"""
     L, st = lib(), _stream()
     T, B, D, U, S, K = a.T, a.B, a.D, a.U, a.S, a.K
     SK, X, f = S * K, U + D, 4
@@ -2158,13 +2186,12 @@ class _ObserveSeq(Function):
         pst = torch.empty(T, B, SK, device=dev)
         stats = torch.empty(6, T, B, device=dev)
         a, w_s, ws = _observe_args((T, B, S, K, D, U), (eps_in, eps_o), W_in, W_g, W_o, W_d, (g_in, be_in, g_g, be_g, g_o, be_o, b_d),
-                                   (sm, xpre, xh, gpre, deter, opre, o, plog), stats, mask=mask, q=q, pst=pst)
-        a.opre_acc = 1
+                                   (sm, xpre, xh, gpre, deter, opre, o, plog), stats, mask=mask, q=q, pst=pst, opre_acc=1)
         copy2d(stoch0, SK, sm, SK, B, SK, mask[0])
         copy2d(deter0, D, xh, X, B, D, mask[0], dst_off=U)
         keep = _scan_fuse(a, w_s, T, B, S, K, U, dev)
         if SEQ_C and gemm_profile is None:
-            check(lib().genrl_observe_seq_fwd(ctypes.byref(a), _stream()), 'observe_seq_fwd')
+            check(lib().genrl_observe_seq_fwd(a, _stream()), 'observe_seq_fwd')
         else:
             _observe_fwd_py(a)
         del keep
@@ -2193,13 +2220,11 @@ class _ObserveSeq(Function):
         gws = torch.empty(lib().genrl_gru_ws_floats(B, D), device=dev)
         a, _, ws = _observe_args((T, B, S, K, D, U), ctx.eps, w_s, W_g, W_o, W_d, (g_in, be_in, g_g, be_g, g_o, be_o, b_d),
                                  (sm, xpre, xh, gpre, deter, opre, o, plog), stats, mask=mask, q=q, d_pst=d_pst, dlg=dlg, dd=dd, dov=dov,
-                                 dopre=dopre, dgpre=dgpre, dxh=dxh, dxpre=dxpre, dgamma=gb[0], dbeta=gb[1], gws=gws)
-        a.opre_acc = 1
-        a.dsa, a.dsb, a.dhd_a, a.dhd_b = ds2[0].data_ptr(), ds2[1].data_ptr(), dh2[0].data_ptr(), dh2[1].data_ptr()
-        a.direct = int(direct)
+                                 dopre=dopre, dgpre=dgpre, dxh=dxh, dxpre=dxpre, dgamma=gb[0], dbeta=gb[1], gws=gws, opre_acc=1,
+                                 dsa=ds2[0], dsb=ds2[1], dhd_a=dh2[0], dhd_b=dh2[1], direct=int(direct))
         if SEQ_C and gemm_profile is None:
             fin = ctypes.c_int(0)
-            check(lib().genrl_observe_seq_bwd(ctypes.byref(a), ctypes.byref(fin), _stream()), 'observe_seq_bwd')
+            check(lib().genrl_observe_seq_bwd(a, ctypes.byref(fin), _stream()), 'observe_seq_bwd')
             fin = fin.value
         else:
             fin = _observe_bwd_py(a)
@@ -2240,7 +2265,7 @@ OBSERVE_FUSE = os.environ.get('GENRL_OBSERVE_FUSE', '1') != '0'     # the scans'
 
 
 def _scan_fuse(a, w_s, T, B, S, K, U, dev):
-    """fill the fused-forward fields of an _ObserveArgs (csrc/seq.hip: six instead of eight launches per step); -> tensors to keep alive"""
+    """fill the fused-forward fields of a genrl_observe (csrc/seq.hip: six instead of eight launches per step); -> tensors to keep alive"""
     if not OBSERVE_FUSE or gemm_precision_is_p16():
         return ()
     keep = []
@@ -2251,10 +2276,10 @@ def _scan_fuse(a, w_s, T, B, S, K, U, dev):
             w_s = w_c
         w_sT = transpose_last2_raw(w_s.reshape(1, U, S * K)).reshape(S * K, U)        # [S K][U]: a latent class = one row
         idx = torch.empty(T, B, S, dtype=torch.int32, device=dev)
-        a.idx, a.w_in_sT = idx.data_ptr(), w_sT.data_ptr()
+        fill(a, idx=idx, w_in_sT=w_sT)
         keep += [w_sT, idx]
     if K == 32 and U % 16 == 0:
-        a.fuse_sample = 1
+        fill(a, fuse_sample=1)
     return tuple(keep)
 
 
@@ -2301,13 +2326,12 @@ def rssm_imagine_seq(act, stoch0, deter0, q, S, K, W_in, b_in, g_in, be_in, W_g,
     pst = torch.empty(T, B, SK, device=dev)
     stats = torch.empty(6, T, B, device=dev)
     a, w_s, ws = _observe_args((T, B, S, K, D, U), (eps_in, eps_out), W_in, W_g, W_out, W_dist, (g_in, be_in, g_g, be_g, g_out, be_out, b_dist),
-                               (sm, xpre, xh, gpre, deter, opre, o, plog), stats, q=q, pst=pst, out_b=b_out)
-    a.opre_acc = 0
+                               (sm, xpre, xh, gpre, deter, opre, o, plog), stats, q=q, pst=pst, out_b=b_out, opre_acc=0)
     copy2d(stoch0, SK, sm, SK, B, SK)
     copy2d(deter0, D, xh, X, B, D, dst_off=U)
     keep = _scan_fuse(a, w_s, T, B, S, K, U, dev)
     if SEQ_C and gemm_profile is None:
-        check(lib().genrl_observe_seq_fwd(ctypes.byref(a), _stream()), 'observe_seq_fwd')
+        check(lib().genrl_observe_seq_fwd(a, _stream()), 'observe_seq_fwd')
     else:
         _observe_fwd_py(a)
     del keep

@@ -11,49 +11,13 @@ import os
 import torch
 from torch.autograd import Function
 
-from ._lib import lib, check
+from ._lib import lib, check, struct as _cstruct
 from . import planes
 from . import planes as pl          # (module alias: `planes=` parameters below are operand handles)
 from . import ops
-from .ops import _p, _f32, _ln_param_targets, _wgrad_target, _bias_grad, sgemm, UNIMIX
+from .ops import _p, _f32, _ln_param_targets, _wgrad_target, _bias_grad, sgemm, fill, UNIMIX
 
 _stream = ops._stream
-
-
-# ---- genrl_rollout (include/genrl_hip.h): the arguments of the rollout's launch loop in C (csrc/seq.hip: genrl_imagine_seq_fwd)
-import ctypes as _ct
-
-
-class _PRef(_ct.Structure):
-    _fields_ = [('p', _ct.c_void_p), ('ld', _ct.c_long), ('plane', _ct.c_long), ('inv', _ct.c_void_p)]
-
-
-_FP, _F, _I = _ct.c_void_p, _ct.c_float, _ct.c_int
-
-
-class _RolloutArgs(_ct.Structure):
-    _fields_ = ([(n, _I) for n in ('H', 'N', 'S', 'K', 'D', 'A', 'AP', 'U', 'L')] + [(n, _F) for n in ('unimix', 'min_std', 'max_std')]
-                + [(n, _FP) for n in ('stoch', 'deter', 'logit', 'action', 'raws', 'eps', 'q')]
-                + [(n, _PRef) for n in ('stoch_p', 'deter_p', 'act_p', 'x_p', 'o_p')]
-                + [(n, _FP) for n in ('x_pre', 'x', 'g_pre', 'o_pre', 'o', 'xm', 'xr', 'gm', 'gr', 'om', 'orr')]
-                + [(n, _PRef) for n in ('w_in_s', 'w_in_a', 'w_g_x', 'w_g_h', 'w_out', 'w_dist')]
-                + [('in_b', _FP), ('in_g', _FP), ('in_be', _FP), ('in_eps', _F), ('gru_g', _FP), ('gru_be', _FP),
-                   ('out_b', _FP), ('out_g', _FP), ('out_be', _FP), ('out_eps', _F), ('dist_b', _FP),
-                   ('pw0s', _PRef), ('pw0d', _PRef), ('pw', _PRef * 8), ('pb', _FP * 8), ('pg', _FP * 8), ('pbe', _FP * 8),
-                   ('peps', _F * 8), ('pU', _I * 8), ('ppre', _FP * 8), ('py', _FP * 8), ('pmean', _FP * 8), ('prstd', _FP * 8),
-                   ('pyp', _PRef * 8), ('head_w', _FP), ('head_b', _FP), ('ln_part', _FP), ('ln_sync', _FP)])
-
-
-class _RolloutBwdArgs(_ct.Structure):
-    _fields_ = ([(n, _I) for n in ('H', 'N', 'S', 'K', 'D', 'A', 'AP', 'U')] + [(n, _F) for n in ('unimix', 'min_std', 'max_std')]
-                + [(n, _FP) for n in ('logit', 'deter', 'raws', 'eps', 'x_pre', 'g_pre', 'o_pre', 'xm', 'xr', 'gm', 'gr', 'om', 'orr',
-                                      'ds', 'dd', 'dl_in', 'dact_all', 'd_raw', 'dlg', 'dov', 'do_pre', 'dg_pre', 'dx', 'dx_pre', 'dha', 'dhb')]
-                + [(n, _PRef) for n in ('dlg_p', 'dop_p', 'dg_p', 'dxp_p', 'wt_dist', 'wt_out', 'wt_g_x', 'wt_g_h', 'wt_in_s')]
-                + [(n, _FP) for n in ('waT', 'out_g', 'out_be', 'gru_g', 'gru_be', 'in_g', 'in_be', 'dx_pre_all')])
-
-
-def _pref(P):
-    return _PRef(P.t.data_ptr(), P.ld, P.plane, P.inv.data_ptr())
 
 
 def _ln_fwd(pre_ptr, gamma, beta, y_ptr, mean_ptr, rstd_ptr, M, N, eps, P, row0):
@@ -183,18 +147,12 @@ class _RolloutPlanes(Function):
     def forward(ctx, stoch0, deter0, logit0, eps, q, spec, head_w, head_b, *actor_params):
         ctx.set_materialize_grads(False)
         sp, tape = spec, spec.tape
-        H, N = tape.H, tape.N
-        S, K = sp.S, sp.K
-        SK, D = S * K, deter0.shape[1]
-        A = eps.shape[-1]
-        U = sp.in_w.shape[0]
         dev = deter0.device
+        dims, bufs, eps, q = ops._rollout_buffers(stoch0, deter0, logit0, eps, q, sp, tape)
+        H, N, S, K, D, A, U, AP = dims
+        stoch, deter, logit, action, raws, x_pre, g_pre, o_pre, st = bufs
+        SK = S * K
         f = lambda *shape: torch.empty(*shape, device=dev)
-        AP = (A + 3) // 4 * 4
-        stoch = f(H + 1, N, SK); deter = f(H + 1, N, D); logit = f(H + 1, N, SK)
-        action = torch.zeros(H + 1, N, AP, device=dev)
-        raws = f(H, N, 2 * A)
-        stoch[0].copy_(stoch0.reshape(N, SK)); deter[0].copy_(deter0); logit[0].copy_(logit0.reshape(N, SK))
         # planes of every GEMM operand, rows h*N + n
         stoch_p, deter_p = planes.Planes((H + 1) * N, SK, dev), planes.Planes((H + 1) * N, D, dev)
         act_p = planes.Planes((H + 1) * N, A, dev)                 # (zero padded to 64 columns; row block 0 unused)
@@ -203,47 +161,32 @@ class _RolloutPlanes(Function):
         # (x and o -- the img_in / img_out activations -- are consumed within the step as PLANES only: no fp32 copy is written where the
         # LayerNorm kernel can do without, 5.9 -> 5.4 us per launch at 1 024 rows)
         planes_only = 256 < U <= 4096 and U % 4 == 0
-        x_pre, x = f(H, N, U), (None if planes_only else f(N, U))
-        g_pre = f(H, N, 3 * D)
-        o_pre, o = f(H, N, U), (None if planes_only else f(N, U))
-        st = {k: f(H, N) for k in ('xm', 'xr', 'gm', 'gr', 'om', 'or')}
-        eps = _f32(eps).contiguous(); q = _f32(q).contiguous()
+        x, o = (None, None) if planes_only else (f(N, U), f(N, U))
         w_in_s, w_in_a = planes.weight(sp.in_w, c0=0, c1=SK), planes.weight(sp.in_w, c0=SK, c1=SK + A)
         w_g_x, w_g_h = planes.weight(sp.gru_w, c0=0, c1=U), planes.weight(sp.gru_w, c0=U)
         w_out, w_dist = planes.weight(sp.out_w), planes.weight(sp.dist_w)
         pt = lambda t, off: t.data_ptr() + 4 * off
         L = lib()
-        seq_c = ops.SEQ_C and planes.gemm_profile is None and len(tape.layers) <= 8
+        seq_c = ops.SEQ_C and planes.gemm_profile is None and len(tape.layers) <= ops._max_layers('genrl_rollout')
         # Dense -> LayerNorm -> SiLU as ONE launch where the shape allows (genrl_gemm_h2_ln: policy layers, img_in, img_out: 10 launches per step)
         fuse_any = planes.ln_fused_here(dev)                 # (per layer: genrl_gemm_h2_ln_ok(N, width), in C and in the Python twin alike)
         fuse_ln = fuse_any and planes.gemm_ln_ok(N, U, dev)
         if seq_c:
             # the H-step launch loop in C (csrc/seq.hip: genrl_imagine_seq_fwd -- the loop below, launch for launch, from one host call)
-            a = _RolloutArgs()
-            a.H, a.N, a.S, a.K, a.D, a.A, a.AP, a.U, a.L = H, N, S, K, D, A, AP, U, len(tape.layers)
-            a.unimix, a.min_std, a.max_std = UNIMIX, sp.min_std, sp.max_std
-            for n_, t_ in (('stoch', stoch), ('deter', deter), ('logit', logit), ('action', action), ('raws', raws), ('eps', eps), ('q', q),
-                           ('x_pre', x_pre), ('x', x), ('g_pre', g_pre), ('o_pre', o_pre), ('o', o), ('xm', st['xm']), ('xr', st['xr']),
-                           ('gm', st['gm']), ('gr', st['gr']), ('om', st['om']), ('orr', st['or']), ('in_b', sp.in_b), ('in_g', sp.in_g),
-                           ('in_be', sp.in_be), ('gru_g', sp.gru_g), ('gru_be', sp.gru_be), ('out_b', sp.out_b), ('out_g', sp.out_g),
-                           ('out_be', sp.out_be), ('dist_b', sp.dist_b), ('head_w', tape.head_w), ('head_b', tape.head_b)):
-                setattr(a, n_, _p(t_))
-            a.in_eps, a.out_eps = sp.in_eps, sp.out_eps
-            for n_, P_ in (('stoch_p', stoch_p), ('deter_p', deter_p), ('act_p', act_p), ('x_p', x_p), ('o_p', o_p), ('w_in_s', w_in_s),
-                           ('w_in_a', w_in_a), ('w_g_x', w_g_x), ('w_g_h', w_g_h), ('w_out', w_out), ('w_dist', w_dist)):
-                setattr(a, n_, _pref(P_))
-            for l, (W_, b_, ga_, be_, eps_) in enumerate(tape.layers):
-                if l == 0:
-                    a.pw0s, a.pw0d = _pref(planes.weight(W_, c0=0, c1=SK)), _pref(planes.weight(W_, c0=SK))
+            common, layers = ops._rollout_fields(sp, tape, dims, bufs, x=x, o=o, eps=eps, q=q)
+            a = fill(_cstruct('genrl_rollout')(), **common, stoch_p=stoch_p, deter_p=deter_p, act_p=act_p, x_p=x_p, o_p=o_p, w_in_s=w_in_s,
+                     w_in_a=w_in_a, w_g_x=w_g_x, w_g_h=w_g_h, w_out=w_out, w_dist=w_dist)
+            for l, fields in enumerate(layers):
+                W_ = tape.layers[l][0]
+                if l == 0:                # layer 0: the stoch / deter column blocks of its weight
+                    fill(a, pw0s=planes.weight(W_, c0=0, c1=SK), pw0d=planes.weight(W_, c0=SK))
                 else:
-                    a.pw[l] = _pref(planes.weight(W_))
-                a.pb[l], a.pg[l], a.pbe[l], a.peps[l], a.pU[l] = _p(b_), _p(ga_), _p(be_), eps_, W_.shape[0]
-                a.ppre[l], a.py[l], a.pmean[l], a.prstd[l] = _p(tape.pre[l]), _p(tape.y[l]), _p(tape.mean[l]), _p(tape.rstd[l])
-                a.pyp[l] = _pref(tape.yp[l])
+                    fill(a, at=l, pw=planes.weight(W_))
+                fill(a, at=l, pyp=tape.yp[l], **fields)
             if fuse_any:
                 sync_, part_ = planes._ln_workspace(dev)
-                a.ln_part, a.ln_sync = (part_.data_ptr() + 15) // 16 * 16, sync_.data_ptr()
-            check(L.genrl_imagine_seq_fwd(_ct.addressof(a), _stream()), 'imagine_seq_fwd')
+                fill(a, ln_part=(part_.data_ptr() + 15) // 16 * 16, ln_sync=sync_.data_ptr())
+            check(L.genrl_imagine_seq_fwd(a, _stream()), 'imagine_seq_fwd')
         for h in (() if seq_c else range(H)):
             r0, r1 = h * N, (h + 1) * N
             tape._forward_planes(h, stoch_p, deter_p, None)
@@ -277,30 +220,18 @@ class _RolloutPlanes(Function):
                 check(L.genrl_onehot_fwd_h2(pt(logit, r1 * SK), pt(q, h * N * SK), pt(stoch, r1 * SK), None, N * S, K, UNIMIX,
                                             stoch_p.ptr(r1), SK, stoch_p.ld, stoch_p.plane, stoch_p.inv_ptr(r1), _stream()),
                       'onehot_fwd_h2')
-        tape.inputs = (stoch, deter)
         tape.state_planes = (stoch_p, deter_p)        # rows h*N + n: the heads evaluated on the rollout take them as operands
-        ctx.sp = sp
-        ctx.bufs = (stoch, deter, logit, raws, eps, x_pre, g_pre, o_pre, st)
-        ctx.nparams = len(actor_params)
-        ctx.dims = (H, N, S, K, D, A, U)
-        # (views, never the buffers themselves: ctx.bufs holds `deter` and `raws`, and an OUTPUT tensor kept on ctx is a reference cycle
-        # through its grad_fn that Python's collector cannot see -- every eager iteration's rollout buffers, 1.4 GiB, stayed alive)
-        return stoch.reshape(H + 1, N, S, K), deter.view(H + 1, N, D), logit.reshape(H + 1, N, S, K), action[:, :, :A], raws.view(H, N, 2 * A)
+        return ops._rollout_outputs(ctx, sp, dims, bufs, eps)
 
     @staticmethod
     def backward(ctx, d_stoch, d_deter, d_logit, d_action, d_raws):
         sp, tape = ctx.sp, ctx.sp.tape
         stoch, deter, logit, raws, eps, x_pre, g_pre, o_pre, st = ctx.bufs
-        H, N, S, K, D, A, U = ctx.dims
+        H, N, S, K, D, A, U, AP = ctx.dims
         SK = S * K
         dev = deter.device
-        AP = (A + 3) // 4 * 4
-        z = lambda *shape: torch.zeros(*shape, device=dev)
         f = lambda *shape: torch.empty(*shape, device=dev)
-        ds = d_stoch.reshape(H + 1, N, SK).clone() if d_stoch is not None else z(H + 1, N, SK)
-        dd = d_deter.clone() if d_deter is not None else z(H + 1, N, D)
-        dl_in = d_logit.reshape(H + 1, N, SK).contiguous() if d_logit is not None else None
-        da_in = d_action.contiguous() if d_action is not None else None
+        ds, dd, dl_in, dact_all, dha, dhb = ops._rollout_upstream(ctx.dims, dev, d_stoch, d_deter, d_logit, d_action)
         # (d o_pre is consumed as planes only: the LayerNorm backward writes no fp32 copy of it where its kernel can do without)
         no_dx = 256 < U <= 4096 and U % 4 == 0
         # (d g_pre has plane readers only -- the two GRU dgrads -- and so has d logits unless an upstream logit gradient is accumulated into
@@ -310,8 +241,7 @@ class _RolloutPlanes(Function):
         # d x_pre of EVERY step: the head's backward, which nothing in the loop waits for, then runs once over all H N rows behind it
         dx_pre = f(H, N, U)
         dlg_p, dop_p, dg_p, dxp_p = planes.Planes(N, SK, dev), planes.Planes(N, U, dev), planes.Planes(N, 3 * D, dev), planes.Planes(N, U, dev)
-        dha, dhb = f(N, D), f(N, D)
-        cur, nxt = dha, None                              # ping-pong: recurrent gradient into deter_h from step h's GRU
+        cur, nxt = dha, None
         # transposed weight planes: rows = the product's output columns
         wt_dist, wt_out = planes.weight(sp.dist_w, True), planes.weight(sp.out_w, True)
         wt_g_x, wt_g_h = planes.weight(sp.gru_w, True, 0, U), planes.weight(sp.gru_w, True, U)
@@ -319,28 +249,17 @@ class _RolloutPlanes(Function):
         waT = sp.in_w.detach()[:, SK:SK + A].t().contiguous()            # (A, U): the action columns, for the fused head backward
         pt = lambda t, off: t.data_ptr() + 4 * off
         L = lib()
-        dact_all = None
-        if da_in is not None:                 # upstream action gradients, once, in rows padded like the forward's actions
-            dact_all = torch.zeros(H + 1, N, AP, device=dev)
-            dact_all[:, :, :A].copy_(da_in)
         seq_c = ops.SEQ_C and planes.gemm_profile is None
         if seq_c:
             # the dgrad chain's launch loop in C (csrc/seq.hip: genrl_imagine_seq_bwd -- the loop below, launch for launch)
-            a = _RolloutBwdArgs()
-            a.H, a.N, a.S, a.K, a.D, a.A, a.AP, a.U = H, N, S, K, D, A, AP, U
-            a.unimix, a.min_std, a.max_std = UNIMIX, sp.min_std, sp.max_std
-            for n_, t_ in (('logit', logit), ('deter', deter), ('raws', raws), ('eps', eps), ('x_pre', x_pre), ('g_pre', g_pre), ('o_pre', o_pre),
-                           ('xm', st['xm']), ('xr', st['xr']), ('gm', st['gm']), ('gr', st['gr']), ('om', st['om']), ('orr', st['or']),
-                           ('ds', ds), ('dd', dd), ('dl_in', dl_in), ('dact_all', dact_all), ('d_raw', tape.d_raw), ('dlg', dlg), ('dov', do),
-                           ('do_pre', do_pre), ('dg_pre', None), ('dx', dx), ('dx_pre', None), ('dx_pre_all', dx_pre), ('dha', dha), ('dhb', dhb),
-                           ('waT', waT),
-                           ('out_g', sp.out_g), ('out_be', sp.out_be), ('gru_g', sp.gru_g), ('gru_be', sp.gru_be), ('in_g', sp.in_g),
-                           ('in_be', sp.in_be)):
-                setattr(a, n_, _p(t_))
-            for n_, P_ in (('dlg_p', dlg_p), ('dop_p', dop_p), ('dg_p', dg_p), ('dxp_p', dxp_p), ('wt_dist', wt_dist), ('wt_out', wt_out),
-                           ('wt_g_x', wt_g_x), ('wt_g_h', wt_g_h), ('wt_in_s', wt_in_s)):
-                setattr(a, n_, _pref(P_))
-            check(L.genrl_imagine_seq_bwd(_ct.addressof(a), _stream()), 'imagine_seq_bwd')
+            # (its forward fields are a subset of the rollout's; dg_pre and dx_pre stay NULL: planes only, and the slab per step instead)
+            common, _ = ops._rollout_fields(sp, tape, ctx.dims, (None, deter, logit, None, raws, x_pre, g_pre, o_pre, st), eps=eps)
+            a = _cstruct('genrl_rollout_bwd')()
+            fill(a, **{n_: common[n_] for n_, _t in a._fields_ if n_ in common},
+                 ds=ds, dd=dd, dl_in=dl_in, dact_all=dact_all, d_raw=tape.d_raw, dlg=dlg, dov=do, do_pre=do_pre, dx=dx, dx_pre_all=dx_pre,
+                 dha=dha, dhb=dhb, waT=waT, dlg_p=dlg_p, dop_p=dop_p, dg_p=dg_p, dxp_p=dxp_p, wt_dist=wt_dist, wt_out=wt_out, wt_g_x=wt_g_x,
+                 wt_g_h=wt_g_h, wt_in_s=wt_in_s)
+            check(L.genrl_imagine_seq_bwd(a, _stream()), 'imagine_seq_bwd')
         for h in (() if seq_c else range(H - 1, -1, -1)):
             r0, r1 = h * N, (h + 1) * N
             if dl_in is not None:
@@ -368,11 +287,7 @@ class _RolloutPlanes(Function):
             check(L.genrl_actor_head_linear_bwd(_p(dx_pre), U, _p(waT), pt(dact_all, N * AP) if dact_all is not None else None, AP,
                                                 _p(raws), _p(eps), _p(tape.d_raw), H * N, U, A, sp.min_std, sp.max_std, _stream()),
                   'actor_head_linear_bwd')
-        if d_raws is not None:
-            tape.d_raw += d_raws
-        dWh, dbh, grads = tape._backward()
-        flat = [g for lg in grads for g in lg]
-        return (None, None, None, None, None, None, dWh, dbh, *flat)
+        return ops._rollout_param_grads(tape, d_raws)
 
 
 class _DenseLNActPlanes(Function):

@@ -7,11 +7,10 @@ the fp16 matrix cores (three MFMAs per block and k-step) with no conversion work
 planes from the producing row kernel (ops: *_h2 entry points); weights are split here, once per optimiser step
 (`weight`, cached until `invalidate()`), also transposed for the dgrad products.  (The first plane format, three bf16 planes with six products --
 "x3" -- is still offered by the kernel, genrl_split_x3 / genrl_gemm_x3, as the exactly-representing variant.)"""
-import ctypes
 import os
 import weakref
 import torch
-from ._lib import lib, check, GenrlHipError
+from ._lib import lib, check, GenrlHipError, struct
 
 ENABLED = os.environ.get('GENRL_PLANES', '1') != '0'
 _amp_saved = None            # ENABLED as it was before a precision-16 agent switched the plane products off (agent/dreamer.py)
@@ -73,12 +72,6 @@ _wcache = {}             # (id(W), transpose, c0, c1) -> [epoch of the split, Pl
 #                          recycled id() can never meet a stale one)
 
 
-class _Desc(ctypes.Structure):          # genrl_split_desc (include/genrl_hip.h)
-    _fields_ = [('src', ctypes.c_void_p), ('ldx', ctypes.c_long), ('R', ctypes.c_int), ('Cn', ctypes.c_int),
-                ('out', ctypes.c_void_p), ('ld_out', ctypes.c_long), ('plane', ctypes.c_long), ('inv', ctypes.c_void_p),
-                ('transpose', ctypes.c_int)]
-
-
 _dcache = {}             # (id(W), tag) -> [epoch, object derived from W, W.data_ptr(), weakref(W), stream that built it, (W._version, extra)]
 
 
@@ -125,12 +118,14 @@ def invalidate(params=None):
 def _split_entries(stale, stream):
     if not stale:
         return
-    arr = (_Desc * len(stale))()
+    arr = (struct('genrl_split_desc') * len(stale))()
     for d, ((_, transpose, c0, c1), ent) in zip(arr, stale):
         W, P = ent[3](), ent[1]
+        # (addresses and scalars, one descriptor per stale weight: assigned directly, several times cheaper than ops.fill(); a name that is
+        # no field raises all the same, _lib)
         d.src, d.ldx, d.R, d.Cn = W.data_ptr() + 4 * c0 * W.stride(1), W.stride(0), W.shape[0], c1 - c0
         d.out, d.ld_out, d.plane, d.inv, d.transpose = P.ptr(0), P.ld, P.plane, P.inv_ptr(0), int(transpose)
-    check(lib().genrl_split_h2_batch(ctypes.cast(arr, ctypes.c_void_p), len(stale), stream), 'split_h2_batch')
+    check(lib().genrl_split_h2_batch(arr, len(stale), stream), 'split_h2_batch')
     for _, ent in stale:
         ent[0], ent[2] = _epoch, ent[3]().data_ptr()
 

@@ -220,6 +220,14 @@ int genrl_gru_seq_bwd(const float* dout, const float* pre, const float* Wh, long
  * then img_step -- [stoch | action] -> hidden, [hidden | deter] -> GRU gates, deter -> hidden -> prior logits + categorical sample -- on
  * plane operands: 16 launches per step (10 with r->ln_sync, below), exactly those of genrl_amd/ops_planes.py::_RolloutPlanes.forward in the same order (bit-identical),
  * from ONE host call.  All buffers are the caller's (genrl_rollout names them); time-major rows h N + n; planes rows likewise. */
+/* BINDING GRAMMAR.  genrl_amd/_lib.py builds the ctypes classes of every argument struct from this text (there is no second definition),
+ * and refuses -- it never skips -- a declaration outside this grammar:
+ *   typedef struct { DECL ... } genrl_NAME;            no tag, no nesting of anonymous structs / unions, defined before its first use
+ *   DECL    = [const] BASE NAME[, NAME ...];           scalars and earlier genrl_* structs by value; each NAME may carry one [N], N a literal
+ *           | [const] BASE* NAME; | [const] BASE* NAME[N];     ONE declarator per pointer declaration, the star written against the type
+ *   BASE    = int | unsigned | long | float | uint16_t | an earlier genrl_NAME  (pointers also: void)
+ * No bit-fields, function pointers, pointers to pointers, enums, macros or preprocessor conditionals inside a struct; comments anywhere.
+ * A function parameter `const genrl_NAME*` binds as a pointer to that class: a call with another struct is a Python TypeError. */
 typedef struct { const uint16_t* p; long ld, plane; const float* inv; } genrl_planes_ref;    /* h2 planes [2][rows][ld] + inverse row scales */
 typedef struct {
   int H, N, S, K, D, A, AP, U, L;                 /* horizon, rows, latents, classes, deter, action dim (AP: padded to 4), hidden, policy layers (<= 8) */

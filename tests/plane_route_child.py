@@ -664,11 +664,8 @@ def run_split(L, log):
             bad.append('wrote past the planes')
         out[cid] = dict(rc=rc, bad=bad)
     # batch: 70 entries, 35 row and 35 transposed ones interleaved: each pass takes two chunks (32 + 3 entries)
-    import ctypes
-
-    class Desc(ctypes.Structure):
-        _fields_ = [('src', ctypes.c_void_p), ('ldx', ctypes.c_long), ('R', ctypes.c_int), ('Cn', ctypes.c_int), ('out', ctypes.c_void_p),
-                    ('ld_out', ctypes.c_long), ('plane', ctypes.c_long), ('inv', ctypes.c_void_p), ('transpose', ctypes.c_int)]
+    from genrl_amd._lib import struct
+    Desc = struct('genrl_split_desc')
     gen = torch.Generator().manual_seed(77)
     ents = []
     descs = (Desc * 70)()
@@ -683,7 +680,7 @@ def run_split(L, log):
         inv = torch.full((Ro + 4,), float('nan'), device='cuda')
         descs[i] = Desc(x.data_ptr(), C, R, C, pl.data_ptr(), ld, Ro * ld, inv.data_ptr(), tr)
         ents.append((X, x, pl, inv, ld, tr, Ro))
-    rc = L.genrl_split_h2_batch(ctypes.cast(descs, ctypes.c_void_p), 70, stream())
+    rc = L.genrl_split_h2_batch(descs, 70, stream())
     torch.cuda.synchronize()
     bad = []
     for i, (X, x, pl, inv, ld, tr, Ro) in enumerate(ents):
