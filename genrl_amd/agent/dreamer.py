@@ -173,9 +173,13 @@ class WorldModel(Module):  # ref :120-321
         self.cfg = config
         self.device = config.device
         self.encoder = common.Encoder(shapes, **config.encoder)
-        key = self.encoder.cnn_keys[0]
-        sizes = common._conv_sizes(shapes[key][-1], config.encoder['cnn_kernels'])
-        embed_dim = 2 ** (len(sizes) - 1) * self.encoder._cnn_depth * sizes[-1] ** 2     # ref :129-132
+        embed_dim = 0
+        if self.encoder.cnn_keys:
+            key = self.encoder.cnn_keys[0]
+            sizes = common._conv_sizes(shapes[key][-1], config.encoder['cnn_kernels'])
+            embed_dim = 2 ** (len(sizes) - 1) * self.encoder._cnn_depth * sizes[-1] ** 2     # ref :129-132
+        if self.encoder.mlp_keys:                # the vector keys' MLP beside, or instead of, the conv stack (ref :610-616)
+            embed_dim += int(self.encoder._mlp_layers[-1])
         self.embed_dim = embed_dim
         self.rssm = common.EnsembleRSSM(**config.rssm, action_dim=act_dim, embed_dim=embed_dim, device=self.device)
         self.heads = {}

@@ -7,7 +7,8 @@ of libgenrl_hip.so (genrl_amd/ops.py).  nn.Module containers (nn.Linear, nn.Conv
 are used only as *parameter holders*: their torch forward is never called on the hot path.
 
 What the GenRL path and the dreamer_v3 / dreamer_v2 defaults configure is implemented (norm 'layer'/'none', act SiLU, discrete or
-continuous latents, GRU cell, dists mse / twohot / normal / trunc_normal / onehot, image_dist mse / normal_unit_std); other reference options raise.
+continuous latents, GRU cell, dists mse / twohot / normal / trunc_normal / onehot / symlog_mse, image_dist mse / normal_unit_std, vector
+observation keys beside or instead of one image key); other reference options raise.
 """
 import contextlib
 import re
@@ -86,7 +87,26 @@ class MSEHeadDist:
         assert self._mode.shape == value.shape, (self._mode.shape, value.shape)
         if self._mode.shape[-1] == 1:
             return ops.sqerr_like(self._mode, value)
-        raise NotImplementedError('mse heads wider than one output are not configured by any shipped defaults')
+        return ops.vec_like(self._mode, value.float(), ops.VEC_LIKE_KINDS['mse'])       # (a decoder's vector key)
+
+
+class SymlogDist:
+    """ref :85-118 with dist 'mse', agg 'sum' over one event dimension (DistLayer 'symlog_mse', :839-840): the head regresses symlog(x);
+    squared differences below `tol` count as 0, in value and in gradient.  mean() / mode() are methods, as the reference has them."""
+    def __init__(self, mode, dims=1, dist='mse', agg='sum', tol=1e-8):
+        assert dims == 1 and dist == 'mse' and agg == 'sum', (dims, dist, agg)
+        self._mode, self._tol = mode, tol
+        self.batch_shape, self.event_shape = mode.shape[:-1], mode.shape[-1:]
+
+    def mode(self):
+        return symexp(self._mode)
+
+    def mean(self):
+        return symexp(self._mode)
+
+    def log_prob(self, value):
+        assert self._mode.shape == value.shape, (self._mode.shape, value.shape)
+        return ops.vec_like(self._mode, value.float(), ops.VEC_LIKE_KINDS['symlog_mse'], self._tol)
 
 
 class TwoHotDist:
@@ -240,6 +260,12 @@ class _MSEHead(_Head):
         return MSEHeadDist(raw.reshape(list(raw.shape[:-1]) + list(self.layer._shape)))
 
 
+class _SymlogMSEHead(_Head):
+    def dist(self, raw):
+        assert len(self.layer._shape) == 1, 'symlog_mse is built for vector keys'
+        return SymlogDist(raw)
+
+
 class _NormalHead(_Head):
     """'normal': std = (max_std - min_std) sigmoid(raw_std + 2) + min_std, ops.actor_*.  trunc ('trunc_normal'): std = 2 sigmoid((raw_std +
     init_std) / 2) + min_std (ref :832), ops.trunc_normal_*; the entropy is the untruncated Normal's and has no one-launch metric kernel."""
@@ -293,7 +319,7 @@ class _OneHotHead(_Head):
 
 
 HEADS = {'mse': _MSEHead, 'twohot': _TwoHotHead, 'normal': _NormalHead, 'trunc_normal': lambda layer: _NormalHead(layer, trunc=True),
-         'onehot': _OneHotHead}
+         'onehot': _OneHotHead, 'symlog_mse': _SymlogMSEHead}
 
 
 # ----------------------------------------------------------------------------- scans (API parity)
@@ -498,6 +524,21 @@ def _conv_sizes(size, kernels, transposed=False):
     return out
 
 
+def _mlp_stack(in_dim, widths, norm, act):
+    """the `_mlp_model` of the reference's Encoder / Decoder (ref :590-602, :672-682): Linear, NormLayer, act per width"""
+    layers, prev = [], in_dim
+    for width in widths:
+        layers += [nn.Linear(prev, width, bias=norm != 'none'), NormLayer(norm, width), get_act(act)]
+        prev = width
+    return nn.Sequential(*layers)
+
+
+def _run_mlp_stack(model, x):
+    for i in range(0, len(model), 3):
+        x = _dense_ln_silu(x, model[i], model[i + 1])
+    return x
+
+
 class Encoder(Module):  # ref :558-628
     def __init__(self, shapes, cnn_keys=r'.*', mlp_keys=r'.*', act='SiLU', norm='none',
                  cnn_depth=48, cnn_kernels=(4, 4, 4, 4), mlp_layers=[400, 400, 400, 400], symlog_inputs=False):
@@ -506,23 +547,51 @@ class Encoder(Module):  # ref :558-628
         self.cnn_keys = [k for k, v in shapes.items() if re.match(cnn_keys, k) and len(v) == 3]
         self.mlp_keys = [k for k, v in shapes.items() if re.match(mlp_keys, k) and len(v) == 1]
         assert act == 'SiLU' and norm == 'layer', 'GenRL path: SiLU + layer norm'
-        assert len(self.mlp_keys) == 0, 'proprio MLP inputs are not on the GenRL pixel path'
+        assert self.cnn_keys or self.mlp_keys, 'no observation key selected'
         self._cnn_depth, self._cnn_kernels = cnn_depth, cnn_kernels
-        layers = []
-        for i, kernel in enumerate(self._cnn_kernels):
-            prev_depth = 3 if i == 0 else 2 ** (i - 1) * self._cnn_depth
-            depth = 2 ** i * self._cnn_depth
-            layers += [nn.Conv2d(prev_depth, depth, kernel, stride=2), ImgChLayerNorm(depth), get_act(act)]
-        self._conv_model = nn.Sequential(*layers)
+        self._mlp_layers, self._symlog_inputs = list(mlp_layers), symlog_inputs
+        if self.cnn_keys:
+            layers = []
+            for i, kernel in enumerate(self._cnn_kernels):
+                prev_depth = 3 if i == 0 else 2 ** (i - 1) * self._cnn_depth
+                depth = 2 ** i * self._cnn_depth
+                layers += [nn.Conv2d(prev_depth, depth, kernel, stride=2), ImgChLayerNorm(depth), get_act(act)]
+            self._conv_model = nn.Sequential(*layers)
+        if self.mlp_keys:           # ref :590-602; the first layer reads the keys side by side, in `shapes` order
+            assert self._mlp_layers, 'vector keys need at least one MLP layer'
+            self._mlp_model = _mlp_stack(sum(shapes[k][0] for k in self.mlp_keys), self._mlp_layers, norm, act)
 
     def forward(self, data):
-        key = self.cnn_keys[0]
-        x = data[key]
-        shape = self.shapes[key]
-        batch_dims = x.shape[:-len(shape)]
-        x = x.reshape((-1,) + tuple(x.shape)[len(batch_dims):])
-        out = self._cnn(x)
-        return out.reshape(tuple(batch_dims) + tuple(out.shape[1:]))
+        out = None
+        if self.cnn_keys:
+            key = self.cnn_keys[0]
+            x = data[key]
+            shape = self.shapes[key]
+            batch_dims = x.shape[:-len(shape)]
+            x = x.reshape((-1,) + tuple(x.shape)[len(batch_dims):])
+            out = self._cnn(x)
+            out = out.reshape(tuple(batch_dims) + tuple(out.shape[1:]))
+        if not self.mlp_keys:
+            return out
+        vec = self._mlp(data)
+        return vec if out is None else torch.cat([out, vec], -1)        # [cnn | mlp], ref :610-616
+
+    def _mlp(self, data):
+        """ref :623-628: the vector keys side by side (symlog'ed with `symlog_inputs`), one launch per key into the first layer's input
+        buffer and no concatenation; a single contiguous fp32 key without symlog is read where it lies"""
+        xs = [data[k] for k in self.mlp_keys]
+        lead = xs[0].shape[:-1]
+        xs = [(x if x.dtype == torch.float32 else x.float()).reshape(-1, x.shape[-1]) for x in xs]
+        if len(xs) == 1 and not self._symlog_inputs and xs[0].is_contiguous():
+            x = xs[0]
+        else:
+            x = torch.empty(xs[0].shape[0], sum(v.shape[1] for v in xs), device=xs[0].device)
+            col = 0
+            for v in xs:
+                ops.symlog_rows(v, out=x, col=col, symlog=self._symlog_inputs)
+                col += v.shape[1]
+        x = _run_mlp_stack(self._mlp_model, x)
+        return x.reshape(tuple(lead) + (x.shape[-1],))
 
     def _cnn(self, x):
         """x: uint8 NCHW frames (x/255-0.5 fused into the first layer's patch gather) or float NCHW."""
@@ -550,24 +619,40 @@ class Decoder(Module):  # ref :631-715
         self.mlp_keys = [k for k, v in shapes.items() if re.match(mlp_keys, k) and len(v) == 1]
         assert act == 'SiLU' and norm == 'layer' and image_dist in ('mse', 'normal_unit_std')
         self._image_dist = image_dist
-        assert len(self.mlp_keys) == 0 and len(self.cnn_keys) == 1
+        assert len(self.cnn_keys) <= 1 and (self.cnn_keys or self.mlp_keys), 'one image key at most, and at least one key'
         self._cnn_depth, self._cnn_kernels = cnn_depth, cnn_kernels
         self.channels = {k: self._shapes[k][0] for k in self.cnn_keys}
-        self._conv_in = nn.Sequential(nn.Linear(embed_dim, 32 * self._cnn_depth))
-        layers, n = [], len(self._cnn_kernels)
-        for i, kernel in enumerate(self._cnn_kernels):
-            prev_depth = 32 * self._cnn_depth if i == 0 else 2 ** (n - (i - 1) - 2) * self._cnn_depth
-            depth = 2 ** (n - i - 2) * self._cnn_depth
-            last = i == n - 1
-            if last:
-                depth = sum(self.channels.values())
-            layers += [nn.ConvTranspose2d(prev_depth, depth, kernel, stride=2),
-                       NormLayer('none', depth) if last else ImgChLayerNorm(depth),
-                       nn.Identity() if last else get_act(act)]
-        self._conv_model = nn.Sequential(*layers)
+        if self.cnn_keys:
+            self._conv_in = nn.Sequential(nn.Linear(embed_dim, 32 * self._cnn_depth))
+            layers, n = [], len(self._cnn_kernels)
+            for i, kernel in enumerate(self._cnn_kernels):
+                prev_depth = 32 * self._cnn_depth if i == 0 else 2 ** (n - (i - 1) - 2) * self._cnn_depth
+                depth = 2 ** (n - i - 2) * self._cnn_depth
+                last = i == n - 1
+                if last:
+                    depth = sum(self.channels.values())
+                layers += [nn.ConvTranspose2d(prev_depth, depth, kernel, stride=2),
+                           NormLayer('none', depth) if last else ImgChLayerNorm(depth),
+                           nn.Identity() if last else get_act(act)]
+            self._conv_model = nn.Sequential(*layers)
+        if self.mlp_keys:           # ref :672-684: one trunk on the features, one DistLayer per vector key
+            assert len(mlp_layers) > 0, 'vector keys need at least one MLP layer'
+            self._mlp_model = _mlp_stack(embed_dim, list(mlp_layers), norm, act)
+            for key in self.mlp_keys:
+                self.add_module(f'dense_{key}', DistLayer(mlp_layers[-1], shapes[key], dist=mlp_dist))
 
     def forward(self, features):
-        return self._cnn(features)
+        if not self.mlp_keys:
+            return self._cnn(features)
+        outputs = self._cnn(features) if self.cnn_keys else {}
+        outputs.update(self._mlp(features))
+        return outputs
+
+    def _mlp(self, features):
+        """ref :708-715: the trunk runs once and every vector key's head reads it"""
+        x = _run_mlp_stack(self._mlp_model, features.reshape(-1, features.shape[-1]))
+        x = x.reshape(tuple(features.shape[:-1]) + (x.shape[-1],))
+        return {key: getattr(self, f'dense_{key}')(x) for key in self.mlp_keys}
 
     def _cnn(self, features):
         lead = features.shape[:-1]

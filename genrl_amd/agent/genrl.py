@@ -6,6 +6,7 @@ model carries a video-language *connector* (VideoSSM) that is trained next to it
 imagination behaviour is rewarded by a language/video target instead of the environment.
 Reference locations are cited per member; the bodies are organised around the batched HIP ops.
 """
+import re
 import torch
 
 from .dreamer import DreamerAgent, ActorCritic, stop_gradient, env_reward
@@ -41,6 +42,11 @@ class GenRLAgent(DreamerAgent):
         if not cfg.rssm.get('discrete', False) or not cfg.connector_rssm.get('discrete', False):
             raise NotImplementedError('GenRLAgent needs discrete latents (`rssm.discrete`, `connector_rssm.discrete`): its connector '
                                       'teacher-forces one-hot latents; continuous latents are built for DreamerAgent and Plan2Explore')
+        for part in ('encoder', 'decoder'):
+            vec = [k for k, v in kwargs['obs_space'].items() if len(v.shape) == 1 and re.match(cfg[part].get('mlp_keys', r'.*'), k)]
+            if vec:
+                raise NotImplementedError(f'GenRLAgent is built on one image key: `{part}.mlp_keys` selects {vec}; vector observations '
+                                          'are built for DreamerAgent and Plan2Explore')
         super().__init__(**kwargs)
         self.n_frames = N_FRAMES
         assert self.cfg.batch_length % self.n_frames == 0, 'Fix batch length param'

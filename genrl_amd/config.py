@@ -135,11 +135,35 @@ def dreamer_cfg(batch_size=64, batch_length=50, device='cuda', task='walker_walk
     return cfg
 
 
-def make_dreamer_agent(cfg, act_dim=6, img=64):
-    from .agent.dreamer import DreamerAgent
+def dreamer_obs_space(img=64, vec_obs=None):
+    """The observation space of the Dreamer agents: the image `observation` and the episode flags.  vec_obs: {key: width} of float32 vector
+    observations added after them (proprioception beside pixels); a key named 'observation' replaces the image (`obs_type: states`)."""
     obs = dict(observation=Spec((3, img, img), np.uint8), is_first=Spec((), bool), is_last=Spec((), bool),
                is_terminal=Spec((), bool))
-    return DreamerAgent(name='dreamer', cfg=cfg, obs_space=obs, act_spec=Spec((act_dim,), np.float32))
+    for key, width in (vec_obs or {}).items():
+        obs[key] = Spec((int(width),), np.float32)
+    return obs
+
+
+def vecobs_overrides(kind, key=None, mlp_layers=None):
+    """encoder / decoder overrides of the two vector-observation setups.  'mix': the image plus the vector key `key` (default
+    'proprio'), symlog inputs and a symlog_mse head.  'states': the vector key `key` (default 'observation') alone, no conv stacks, plain
+    inputs and an mse head.  mlp_layers: the widths of both MLPs (None: the defaults' four layers of 400)."""
+    assert kind in ('mix', 'states'), kind
+    if kind == 'mix':
+        enc = dict(mlp_keys=key or 'proprio', symlog_inputs=True)
+        dec = dict(mlp_keys=key or 'proprio', mlp_dist='symlog_mse')
+    else:
+        enc = dict(cnn_keys='$^', mlp_keys=key or 'observation', symlog_inputs=False)
+        dec = dict(cnn_keys='$^', mlp_keys=key or 'observation', mlp_dist='mse')
+    if mlp_layers is not None:
+        enc['mlp_layers'], dec['mlp_layers'] = list(mlp_layers), list(mlp_layers)
+    return dict(encoder=enc, decoder=dec)
+
+
+def make_dreamer_agent(cfg, act_dim=6, img=64, vec_obs=None):
+    from .agent.dreamer import DreamerAgent
+    return DreamerAgent(name='dreamer', cfg=cfg, obs_space=dreamer_obs_space(img, vec_obs), act_spec=Spec((act_dim,), np.float32))
 
 
 def dreamer_tiny_overrides():
@@ -156,8 +180,6 @@ def p2e_cfg(batch_size=64, batch_length=50, device='cuda', task='walker_walk', *
     return dreamer_cfg(batch_size, batch_length, device, task, **base)
 
 
-def make_p2e_agent(cfg, act_dim=6, img=64):
+def make_p2e_agent(cfg, act_dim=6, img=64, vec_obs=None):
     from .agent.plan2explore import Plan2Explore
-    obs = dict(observation=Spec((3, img, img), np.uint8), is_first=Spec((), bool), is_last=Spec((), bool),
-               is_terminal=Spec((), bool))
-    return Plan2Explore(name='plan2explore', cfg=cfg, obs_space=obs, act_spec=Spec((act_dim,), np.float32))
+    return Plan2Explore(name='plan2explore', cfg=cfg, obs_space=dreamer_obs_space(img, vec_obs), act_spec=Spec((act_dim,), np.float32))

@@ -2659,3 +2659,60 @@ def gauss_entropy(std):
     check(lib().genrl_gauss_kl_fwd(None, _p(sd), None, None, None, _p(ent), None, R, S, _stream()), 'gauss_kl_fwd')
     ent = ent.reshape(sd.shape[:-1])
     return ent.transpose(0, 1) if tm else ent
+
+
+# ------------------------------------------------------------------ vector (1-D) observations (csrc/vecobs.hip)
+
+def symlog_rows(x, out=None, col=0, symlog=True):
+    """The encoder's MLP input (agent/dreamer_utils.py:623-628): x (..., D) -> symlog(x) (symlog False: a copy) as rows of a 2-D buffer.
+    out None: a new (..., D) tensor.  out (R, W): written into its columns col .. col + D (any col: the kernel picks its access width), the
+    concatenation of several keys without a copy; returns out.  Observations carry no gradient."""
+    x2, ldx = _rows_pitch(_f32(x.detach()).reshape(-1, x.shape[-1]))
+    R, D = x2.shape
+    if out is None:
+        y = torch.empty(R, D, device=x.device)
+        dst, res = y, y.view(x.shape)
+    else:
+        assert out.dim() == 2 and out.shape[0] == R and 0 <= col and col + D <= out.shape[1] and out.stride(1) == 1, (out.shape, col, x.shape)
+        _f32(out)
+        dst, res = out[:, col:col + D], out
+    _on_gpu(x2, dst)
+    check(lib().genrl_symlog_rows(_prows(x2), ldx, _prows(dst), dst.stride(0), R, D, int(bool(symlog)), _stream()), 'symlog_rows')
+    return res
+
+
+VEC_LIKE_KINDS = {'mse': 0, 'symlog_mse': 1}
+
+
+class _VecLike(Function):
+    """log_prob of a D-wide vector head as one node: MSEDist (kind 0, agent/dreamer_utils.py:62-83) or SymlogDist 'mse' / 'sum' (kind 1,
+    :85-118) -> -sum_d dist of shape mode.shape[:-1]; backward: one elementwise launch"""
+    @staticmethod
+    def forward(ctx, mode, x, kind, tol):
+        D = mode.shape[-1]
+        assert mode.shape == x.shape and D > 0, (mode.shape, x.shape)
+        _on_gpu(mode, x)
+        m2, ldm = _rows_pitch(_f32(mode).reshape(-1, D))
+        x2, ldx = _rows_pitch(_f32(x).reshape(-1, D))
+        R = m2.shape[0]
+        like = torch.empty(R, device=mode.device)
+        check(lib().genrl_vec_like_fwd(_prows(m2), ldm, _prows(x2), ldx, _p(like), R, D, kind, tol, _stream()), 'vec_like_fwd')
+        ctx.save_for_backward(m2, x2)
+        ctx.cfg = (kind, tol, ldm, ldx, mode.shape)
+        return like.reshape(mode.shape[:-1])
+
+    @staticmethod
+    def backward(ctx, g):
+        m2, x2 = ctx.saved_tensors
+        kind, tol, ldm, ldx, shape = ctx.cfg
+        R, D = m2.shape
+        g = _f32(g).reshape(R).contiguous()
+        d = torch.empty(R, D, device=m2.device)
+        check(lib().genrl_vec_like_bwd(_prows(m2), ldm, _prows(x2), ldx, _p(g), _p(d), D, R, D, kind, tol, 0, _stream()), 'vec_like_bwd')
+        return d.reshape(shape), None, None, None
+
+
+def vec_like(mode, x, kind, tol=1e-8):
+    """mode, x (..., D) -> log_prob of shape (...): kind 0 -(mode - x)^2, kind 1 -(mode - symlog(x))^2 with terms below tol dropped, summed
+    over D.  The target is detached; a column slice of a padded ops.linear output is read in place."""
+    return _VecLike.apply(mode, x.detach(), int(kind), float(tol))

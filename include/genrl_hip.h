@@ -714,6 +714,26 @@ int genrl_gauss_kl_fwd(const float* mean_l, const float* std_l, const float* mea
 int genrl_gauss_kl_bwd(const float* mean_l, const float* std_l, const float* mean_r, const float* std_r, const float* gp,
                        const float* gq, float* dmean_l, float* dstd_l, float* dmean_r, float* dstd_r, long R, int S, void* stream);
 
+/* ---- vector (1-D) observations (encoder `mlp_keys` / `symlog_inputs`, decoder `mlp_keys` / `mlp_dist: mse | symlog_mse`,
+ * agent/dreamer_utils.py:558-715, :62-118; genrl_amd/csrc/vecobs.hip).  Rows of D >= 1 floats with independent row pitches (in floats,
+ * each >= D), so that an operand may be a column slice of a wider buffer; columns past D are neither read nor written.  No alignment is
+ * required of any pointer, D or pitch.  Every entry returns 1 before any launch for D < 1, R < 0, a pitch below D, a missing pointer, a kind
+ * other than 0 / 1 or a tol that is negative or NaN; R == 0 returns 0 without a launch.  Inputs and outputs must not overlap.
+ * genrl_symlog_rows: y[r, :D] = symlog ? sign(x) log(|x| + 1) : x, with |x| + 1 rounded to fp32 before the logarithm (the arithmetic of
+ *   the two-hot kernels' symlog; not log1p).  NaN stays NaN.  16-byte accesses are used when x, y, D and both pitches allow them.
+ * genrl_vec_like_fwd: like[r] = -sum_d dist(mode[r, d], x[r, d]).  kind 0: MSEDist on a D-wide head, dist = (mode - x)^2.  kind 1:
+ *   SymlogDist 'mse' with agg 'sum', dist = (mode - symlog(x))^2 replaced by 0 where it is below tol (the reference's 1e-8).  Target
+ *   and difference are taken in double from the fp32 operands and the sum is accumulated in double in a fixed order: results are
+ *   bit-reproducible, and a row with mode == target gives exactly 0 (kind 1: a mode that is the fp32 symlog of x lies below tol).
+ *   R <= 2^32.
+ * genrl_vec_like_bwd: dmode[r, d] = -2 (mode - t) g[r], t = x or symlog(x); for kind 1 exactly 0 where (mode - t)^2 < tol (decided by
+ *   the forward's expression).  Elementwise; accumulate != 0 adds into dmode, as genrl_onehot_logp_ent_bwd does.  No gradient to x. */
+int genrl_symlog_rows(const float* x, long ldx, float* y, long ldy, long R, int D, int symlog, void* stream);
+int genrl_vec_like_fwd(const float* mode, long ldm, const float* x, long ldx, float* like, long R, int D, int kind, float tol,
+                       void* stream);
+int genrl_vec_like_bwd(const float* mode, long ldm, const float* x, long ldx, const float* g, float* dmode, long lddm, long R, int D,
+                       int kind, float tol, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
