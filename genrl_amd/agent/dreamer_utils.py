@@ -7,7 +7,7 @@ of libgenrl_hip.so (genrl_amd/ops.py).  nn.Module containers (nn.Linear, nn.Conv
 are used only as *parameter holders*: their torch forward is never called on the hot path.
 
 What the GenRL path and the dreamer_v3 / dreamer_v2 defaults configure is implemented (norm 'layer'/'none', act SiLU, discrete or
-continuous latents, GRU cell, dists mse / twohot / normal / trunc_normal / onehot / symlog_mse, image_dist mse / normal_unit_std, vector
+continuous latents, GRU cell, dists mse / twohot / normal / trunc_normal / tanh_normal / onehot / symlog_mse, image_dist mse / normal_unit_std, vector
 observation keys beside or instead of one image key); other reference options raise.
 """
 import contextlib
@@ -221,6 +221,21 @@ class NormalDist:
 TruncNormalDist = NormalDist
 
 
+class TanhNormalDist(NormalDist):
+    """SampleDist(Independent(SquashedNormal(mean, std), 1)) of DistLayer 'tanh_normal' (ref :824-829, :28-60; tools/utils.py:126-170), from
+    the head's raw output: `sample` is the reparameterised tanh(mean + std eps); `mean` and `entropy()` are Monte-Carlo estimates over the
+    head's K samples, drawn at sites of their own on every call, as the reference redraws them."""
+    @property
+    def mean(self):
+        return self.head.mean(self.raw, site=f'{self.site}.mean_eps')
+
+    def entropy(self):
+        return self.head.entropy_grad(self.raw, site=f'{self.site}.ent_eps')[..., 0]
+
+    def mode(self):          # (the reference's raises too: SquashedNormal has no `expand`, ref :45-47; nothing calls it)
+        raise NotImplementedError('mode() of a tanh_normal head')
+
+
 # ----------------------------------------------------------------------------- policy / output heads
 
 class _Head:
@@ -300,6 +315,34 @@ class _NormalHead(_Head):
         return NormalDist(raw, self)
 
 
+class _TanhNormalHead(_Head):
+    """'tanh_normal': the squashed Gaussian tanh(N(5 tanh(out / 5), softplus(raw_std + init_std) + min_std)) (ref :824-829), ops.tanh_normal_*.
+    Its mean and entropy are SampleDist's estimates over K samples (ref :28-60): each call draws its own (K, ..., A) noise, as K times
+    the leading dimensions by (rows, A) -- the reference's (K, ..., rows, A) memory, batch rows in dimension 1 (noise._ROWS_DIM1)."""
+    has_std, noise = True, ('normal', 'imag.act_eps')
+    K = 100                  # SampleDist's `samples` (ref :29)
+
+    def params(self):
+        return self.layer._min_std, self.layer._init_std
+
+    def mc_eps(self, raw, site):
+        lead, A = tuple(raw.shape[:-1]), raw.shape[-1] // 2
+        eps = noise.draw('normal', site, (self.K * int(np.prod(lead[:-1])), lead[-1], A), raw.device)
+        return eps.reshape((self.K,) + lead + (A,))
+
+    def sample(self, raw, eps):
+        return ops.tanh_normal_sample(raw, eps, *self.params())
+
+    def mean(self, raw, site='imag.act_mean_eps'):          # (random: what act(eval_mode=True) and imagine(eval_policy=True) use)
+        return ops.tanh_normal_mc_mean(raw, self.mc_eps(raw, site), *self.params())
+
+    def entropy_grad(self, raw, site='actor.ent_eps'):
+        return ops.tanh_normal_entropy(raw, self.mc_eps(raw, site), *self.params())[..., None]
+
+    def dist(self, raw):
+        return TanhNormalDist(raw, self)
+
+
 class _OneHotHead(_Head):
     """`discrete_actions`: the logits of a unimix categorical; its draws are exponential-race noise from a site of their own"""
     planes_linear, reinforce, noise = True, True, ('exp', 'imag.act_q')
@@ -319,7 +362,7 @@ class _OneHotHead(_Head):
 
 
 HEADS = {'mse': _MSEHead, 'twohot': _TwoHotHead, 'normal': _NormalHead, 'trunc_normal': lambda layer: _NormalHead(layer, trunc=True),
-         'onehot': _OneHotHead, 'symlog_mse': _SymlogMSEHead}
+         'tanh_normal': _TanhNormalHead, 'onehot': _OneHotHead, 'symlog_mse': _SymlogMSEHead}
 
 
 # ----------------------------------------------------------------------------- scans (API parity)

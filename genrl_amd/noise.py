@@ -105,7 +105,9 @@ _static_dp = (0, 1)
 # sites whose tensors are time-major (T or H first): their rows (b-major) sit in dimension 1; everywhere else in 0
 _ROWS_DIM1 = {'wm.post_q', 'wm.prior_q', 'imag.act_eps', 'imag.act_q', 'imag.step_q', 'rssm.imagine_q',
               # continuous latents ('normal'): (T, B, S) posterior / prior noise of a scan, (H, N, S) of an imagined rollout
-              'wm.post_eps', 'wm.prior_eps', 'imag.step_eps', 'rssm.imagine_eps'}
+              'wm.post_eps', 'wm.prior_eps', 'imag.step_eps', 'rssm.imagine_eps',
+              # the tanh_normal head's Monte-Carlo draws: (K (H-1), N, A) entropy noise of the actor loss, (K, rows, A) of a mean
+              'actor.ent_eps', 'actor.mean_eps', 'imag.act_mean_eps'}
 
 
 @contextlib.contextmanager

@@ -986,7 +986,7 @@ def maxcos(u, v, urow=None):
 # ------------------------------------------------------------------ actor head
 
 class _ActorHead(Function):
-    """The sample of a Normal policy head from raw = [out | std_raw].  kind, _ACTOR_HEAD or _TRUNC_HEAD below: (C entry point pair, the
+    """The sample of a Normal policy head from raw = [out | std_raw].  kind, _ACTOR_HEAD, _TRUNC_HEAD or _TANH_HEAD below: (C entry point pair, the
     backward's pick from the two std parameters, what eps / the upstream gradient / mean_std's raw pass through)"""
     @staticmethod
     def forward(ctx, raw, eps, kind, p0, p1):
@@ -1022,6 +1022,7 @@ def _actor_mean_std(raw, kind, p0, p1):
 
 _ACTOR_HEAD = ('actor_head', lambda min_std, max_std: (min_std, max_std), lambda t: t)
 _TRUNC_HEAD = ('trunc_normal_head', lambda min_std, init_std: (init_std,), _f32)
+_TANH_HEAD = ('tanh_normal_head', lambda min_std, init_std: (min_std, init_std), _f32)
 
 
 def actor_sample(raw, eps, min_std=0.1, max_std=1.0):
@@ -1042,6 +1043,65 @@ def trunc_normal_sample(raw, eps, min_std=0.1, init_std=0.0):
 def trunc_normal_mean_std(raw, min_std=0.1, init_std=0.0):
     """-> tanh(out), 2 sigmoid((std_raw + init_std) / 2) + min_std (no gradient: acting, eval_policy, metrics)"""
     return _actor_mean_std(raw, _TRUNC_HEAD, min_std, init_std)
+
+
+# ---- the squashed-Gaussian head (squashed.hip): DistLayer 'tanh_normal', SquashedNormal in SampleDist
+
+def tanh_normal_sample(raw, eps, min_std=0.1, init_std=0.0):
+    """raw (..., 2A) = [out | std_raw] -> tanh(mean + std eps), mean = 5 tanh(out / 5), std = softplus(std_raw + init_std) + min_std:
+    the reparameterised sample of SquashedNormal (tools/utils.py:156-170)"""
+    return _ActorHead.apply(raw, eps, _TANH_HEAD, float(min_std), float(init_std))
+
+
+def tanh_normal_mean_std(raw, min_std=0.1, init_std=0.0):
+    """-> the base Normal's mean 5 tanh(out / 5) and std (no gradient: metrics, tests)"""
+    return _actor_mean_std(raw, _TANH_HEAD, min_std, init_std)
+
+
+def _mc_rows(raw, eps):
+    """raw (..., 2A), eps (K, ..., A) -> contiguous raw [R, 2A], eps [K, R, A] and R, A, K"""
+    r2 = _f32(raw).reshape(-1, raw.shape[-1]).contiguous()
+    R, A = r2.shape[0], r2.shape[1] // 2
+    K = eps.shape[0]
+    assert eps.numel() == K * R * A and eps.shape[-1] == A, (tuple(eps.shape), tuple(raw.shape))
+    return r2, _f32(eps).reshape(K, R, A).contiguous(), R, A, K
+
+
+def tanh_normal_mc_mean(raw, eps, min_std=0.1, init_std=0.0):
+    """SampleDist.mean (agent/dreamer_utils.py:40-43): the mean over the K samples eps (K, ..., A) of tanh(mean + std eps) -> (..., A).
+    No gradient."""
+    r2, e, R, A, K = _mc_rows(raw.detach(), eps)
+    out = torch.empty(R, A, device=raw.device)
+    check(lib().genrl_tanh_normal_mc_fwd(_p(r2), _p(e), None, _p(out), R, A, K, float(min_std), float(init_std), _stream()),
+          'tanh_normal_mc_fwd')
+    return out.reshape(*raw.shape[:-1], A)
+
+
+class _TanhNormalEntropy(Function):
+    @staticmethod
+    def forward(ctx, raw, eps, min_std, init_std):
+        r2, e, R, A, K = _mc_rows(raw, eps)
+        ent = torch.empty(R, device=raw.device)
+        check(lib().genrl_tanh_normal_mc_fwd(_p(r2), _p(e), _p(ent), None, R, A, K, min_std, init_std, _stream()), 'tanh_normal_mc_fwd')
+        ctx.save_for_backward(r2, e)
+        ctx.cfg = (min_std, init_std, raw.shape)
+        return ent.reshape(raw.shape[:-1])
+
+    @staticmethod
+    def backward(ctx, g):
+        r2, e = ctx.saved_tensors
+        min_std, init_std, rshape = ctx.cfg
+        K, R, A = e.shape
+        d = torch.empty_like(r2)
+        check(lib().genrl_tanh_normal_ent_bwd(_p(_f32(g).reshape(R).contiguous()), _p(r2), _p(e), _p(d), R, A, K, min_std, init_std, 0,
+                                              _stream()), 'tanh_normal_ent_bwd')
+        return d.reshape(rshape), None, None, None
+
+
+def tanh_normal_entropy(raw, eps, min_std=0.1, init_std=0.0):
+    """SampleDist.entropy (agent/dreamer_utils.py:54-57): -mean_k log_prob(sample_k) over the K samples eps (K, ..., A) -> (...,), with
+    the gradient to raw through the samples and the density (one launch each way, recomputed from eps)"""
+    return _TanhNormalEntropy.apply(raw, eps, float(min_std), float(init_std))
 
 
 # ---- the imagination rollout's autograd node, the part its two operand kinds share (_Rollout below: fp32 matrices, genrl_rollout_f32;

@@ -667,6 +667,31 @@ int genrl_trunc_normal_head_bwd(const float* daction, const float* raw, const fl
 int genrl_sqerr_fwd(const float* out, const float* x, float* like, long n, void* stream);
 int genrl_sqerr_bwd(const float* out, const float* x, const float* g, float* dout, long n, void* stream);
 
+/* ---- the squashed-Gaussian actor head (DistLayer 'tanh_normal', agent/dreamer_utils.py:824-829: SquashedNormal, tools/utils.py:126-170, in
+ * SampleDist, agent/dreamer_utils.py:28-60; genrl_amd/csrc/squashed.hip).  raw [R, 2A] = [out | std_raw], 1 <= A <= 64:
+ *   mean = 5 tanh(out / 5), std = softplus(std_raw + init_std) + min_std (torch's softplus: the identity above 20), x = mean + std eps,
+ *   action = tanh(x).  Every entry returns 1 before any launch, and writes nothing, for A out of range, K < 1, a missing required pointer
+ *   or no output at all; R = 0 is a no-op.  No NaN or inf for any finite input (out = +-50, std_raw = 25 or -30, eps = +-6, x < -10).
+ * genrl_tanh_normal_head_{fwd,bwd}: the shape of genrl_trunc_normal_head_* above: eps [R, A], action rows ld_action apart (0 = A); any of
+ *   action / mean / std may be NULL.  eps NULL: the mean form (action, if given, = tanh(mean)).  bwd: draw [R, 2A] from daction (rows
+ *   ld_action apart): dx = daction (1 - action^2), d mean = dx, d std = dx eps, then through 5 tanh(. / 5) and the softplus.
+ * genrl_tanh_normal_mc_fwd: SampleDist over K samples, eps [K, R, A]: mean_action[R, A] = mean_k tanh(x_k) (SampleDist.mean) and
+ *   ent[R] = -mean_k log_prob(sample_k) (SampleDist.entropy), log_prob = sum_a(-(x - mean)^2 / (2 std^2) - log std - log(2 pi) / 2 - ladj(x))
+ *   with ladj(x) = 2 (log 2 - x - softplus(-2x)), on the pre-tanh x (no atanh).  ent or mean_action may be NULL.  One row per aligned
+ *   group of 4 ... 64 lanes, one action dimension per lane; per-sample terms are summed in double in the order of k and across the row by
+ *   shuffles in a fixed order: two launches on the same inputs agree bit for bit.
+ * genrl_tanh_normal_ent_bwd: draw [R, 2A] (+)= gent[r] d ent[r] / d raw, recomputed from raw and eps (nothing else is saved):
+ *   d ent / d mean_a = mean_k(-2 tanh x_ka), d ent / d std_a = 1 / std_a + mean_k(-2 tanh(x_ka) eps_ka), then through the head.
+ *   accumulate != 0 adds into draw, as genrl_onehot_logp_ent_bwd does. */
+int genrl_tanh_normal_head_fwd(const float* raw, const float* eps, float* action, float* mean, float* std, long R, int A,
+                               float min_std, float init_std, long ld_action, void* stream);
+int genrl_tanh_normal_head_bwd(const float* daction, const float* raw, const float* eps, float* draw, long R, int A, float min_std,
+                               float init_std, long ld_action, void* stream);
+int genrl_tanh_normal_mc_fwd(const float* raw, const float* eps, float* ent, float* mean_action, long R, int A, int K, float min_std,
+                             float init_std, void* stream);
+int genrl_tanh_normal_ent_bwd(const float* gent, const float* raw, const float* eps, float* draw, long R, int A, int K, float min_std,
+                              float init_std, int accumulate, void* stream);
+
 /* ---- discrete actions (`discrete_actions`, agent/dreamer.py:332-333; `actor_grad: reinforce`, :413-419; genrl_amd/csrc/discrete.hip)
  * genrl_onehot_logp_ent_{fwd,bwd}: the actor's OneHotDist (agent/dreamer_utils.py:177-197) on logits [G, K], 2 <= K <= 64 (returns 1
  *   otherwise and writes nothing): p = (1 - unimix) softmax(logits) + unimix / K, renormalised as torch's Categorical(probs=) does.  Here
