@@ -2,13 +2,12 @@
 
 Every translation unit is compiled to its own object (in parallel, rebuilt only when it or a header changed) and the objects are linked
 into the one shared library the ctypes stub loads; there are no device calls across translation units, so no relocatable device code."""
-import os, subprocess, sys
+import glob, os, subprocess, sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = ['gemm.hip', 'gemm_planes.hip', 'gemm_planes_tn.hip', 'rowops.hip', 'dist.hip', 'conv.hip', 'optim.hip', 'stats.hip', 'seq.hip', 'ensemble.hip',
-       'normfree.hip', 'discrete.hip', 'gaussian.hip', 'vecobs.hip', 'squashed.hip']
-HDR = ['common.h']
+       'rowact.hip', 'discrete.hip', 'gaussian.hip', 'vecobs.hip', 'heads.hip']
 OUT = os.path.join(HERE, 'libgenrl_hip.so')
 OBJ = os.path.join(HERE, 'csrc', 'build')
 
@@ -23,7 +22,7 @@ def _obj(f):
 
 def _hdr_time():
     inc = os.path.join(os.path.dirname(HERE), 'include', 'genrl_hip.h')
-    return max(os.path.getmtime(p) for p in [_src(h) for h in HDR] + [inc])
+    return max(os.path.getmtime(p) for p in glob.glob(_src('*.h')) + [inc])        # every header makes every object stale
 
 
 def _stale(f):

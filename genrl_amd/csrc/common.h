@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -76,6 +77,20 @@ __device__ __forceinline__ void h2_store1(const PlaneOut& o, long idx, float v, 
 }
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// workgroups of a kernel that walks rows grid-strided: one per row up to the file's cap
+static inline int row_grid(long rows, int cap) { return rows < cap ? (int)rows : cap; }
+// an optional plane output (yp != NULL) of a row kernel over N columns that cannot be written
+static inline bool bad_planes(const uint16_t* yp, long ldp, const float* inv, int N) { return yp && (!inv || (ldp & 3) || ldp < N); }
+// f(integral_constant<W>) for the narrowest lane group W = 4 .. 64 that holds n (n > 64: 64; a caller that cannot stride refuses it first)
+template <typename F>
+int dispatch_w(int n, F&& f) {
+  if (n <= 4) return f(std::integral_constant<int, 4>{});
+  if (n <= 8) return f(std::integral_constant<int, 8>{});
+  if (n <= 16) return f(std::integral_constant<int, 16>{});
+  if (n <= 32) return f(std::integral_constant<int, 32>{});
+  return f(std::integral_constant<int, 64>{});
+}
 
 // 64-lane wave reductions (wave = 64 on CDNA; hard-coded).
 __device__ __forceinline__ float wave_sum(float v) {
@@ -110,6 +125,13 @@ __device__ __forceinline__ float group_max(float v) {
   return v;
 }
 
+template <int W>
+__device__ __forceinline__ double group_sum_d(double v) {
+#pragma unroll
+  for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
 // block-wide sum for 256-thread blocks; `red` is >= 8 floats of LDS. All threads get the result.
 __device__ __forceinline__ float block_sum_256(float v, float* red) {
   v = wave_sum(v);
@@ -121,6 +143,28 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
   return r;
 }
 
+// double sum over a 1024-thread workgroup (red: 16 doubles of LDS), the waves added in order.  All threads get the result.
+__device__ __forceinline__ double block_sum_d(double v, double* red) {
+  v = group_sum_d<64>(v);
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  __syncthreads();
+  if (l == 0) red[w] = v;
+  __syncthreads();
+  double r = 0.0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) r += red[i];
+  return r;
+}
+
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+// second sweep of a two-sweep row kernel (256 threads, nv float4 per row): planes of the row this thread has just written
+__device__ __forceinline__ void planes_of_row(const float* yr, int nv, const PlaneOut& xo, long row, float amax, float* red) {
+  const float inv = h2_inv_of(block_max_256(amax, red)), sc = h2_scale_of(inv);
+  for (int j = threadIdx.x; j < nv; j += 256) h2_store4(xo, row, 4 * j, ld4(yr + 4 * j), sc);
+  if (threadIdx.x == 0) xo.inv[row] = inv;
+}
+
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ float siluf_(float x) { return x * sigmoidf_(x); }
 // d/dx silu(x)
@@ -128,3 +172,9 @@ __device__ __forceinline__ float dsiluf_(float x) {
   float s = sigmoidf_(x);
   return s * (1.0f + x * (1.0f - s));
 }
+// sign(x) log(|x| + 1) and its inverse: |x| + 1 is rounded to fp32 first, as the reference and the oracle do (no log1p)
+__device__ __forceinline__ float symlogf_(float x) { return copysignf(logf(fabsf(x) + 1.0f), x); }
+__device__ __forceinline__ float symexpf_(float x) { return copysignf(expf(fabsf(x)) - 1.0f, x); }
+// torch.nn.functional.softplus (beta 1, threshold 20) and its derivative
+__device__ __forceinline__ float softplusf_(float z) { return z > 20.0f ? z : log1pf(expf(z)); }
+__device__ __forceinline__ float dsoftplusf_(float z) { return z > 20.0f ? 1.0f : sigmoidf_(z); }

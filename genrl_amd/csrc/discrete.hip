@@ -5,7 +5,6 @@
 // summation order and double accumulation.  No allocation, no synchronisation with the host, no atomics.
 #include "common.h"
 #include <math.h>
-#include <type_traits>
 
 namespace {
 
@@ -80,33 +79,11 @@ __global__ __launch_bounds__(256) void logp_ent_bwd_kernel(const float* __restri
   if (valid) dlogits[gi * K + k] = accumulate ? dlogits[gi * K + k] + d : d;
 }
 
-template <typename F>
-int dispatch_w(int K, F&& f) {
-  if (K <= 4) return f(std::integral_constant<int, 4>{});
-  if (K <= 8) return f(std::integral_constant<int, 8>{});
-  if (K <= 16) return f(std::integral_constant<int, 16>{});
-  if (K <= 32) return f(std::integral_constant<int, 32>{});
-  return f(std::integral_constant<int, 64>{});
-}
-
 // ---- REINFORCE objective on lambda-returns (agent/dreamer.py:400-429, actor_grad 'reinforce') ----
 //   nt = (target - offset) / scale, nb = (baseline - offset) / scale   [H, N]  (os == null: offset 0, scale 1);
 //   loss = -mean_{h >= 1}( weight[h-1] (logp[h-1] (nt[h] - nb[h]) + ent_scale ent[h-1]) )
 // out[0], out[1] = mean, unbiased std of nt over all H*N (the 'normed_target_*' metrics; written only with os).
 constexpr int NT = 1024;
-
-__device__ __forceinline__ double block_sum_d(double v, double* red /* 16 doubles */) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  __syncthreads();
-  if (l == 0) red[w] = v;
-  __syncthreads();
-  double r = 0.0;
-#pragma unroll
-  for (int i = 0; i < NT / 64; ++i) r += red[i];
-  return r;
-}
 
 __device__ __forceinline__ float advantage(float t, float b, const float* os) {
   return os ? (t - os[0]) / os[1] - (b - os[0]) / os[1] : t - b;

@@ -272,9 +272,6 @@ __global__ __launch_bounds__(256) void cat_kl_bwd_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------ two-hot symlog head (255 bins)
-__device__ __forceinline__ float symlogf_(float x) { return copysignf(logf(fabsf(x) + 1.0f), x); }
-__device__ __forceinline__ float symexpf_(float x) { return copysignf(expf(fabsf(x)) - 1.0f, x); }
-
 struct TwoHot {
   int below, above;
   float wb, wa;
@@ -609,15 +606,7 @@ __global__ __launch_bounds__(256) void align_index_kernel(const float* __restric
   for (int tau = threadIdx.x; tau < T; tau += 256) urow[(long)tau * N + n] = (long)max(tau - bt, 0) * N + n;
 }
 
-template <typename F>
-int dispatch_w(int K, F&& f) {
-  if (K <= 4) return f(std::integral_constant<int, 4>{});
-  if (K <= 8) return f(std::integral_constant<int, 8>{});
-  if (K <= 16) return f(std::integral_constant<int, 16>{});
-  if (K <= 32) return f(std::integral_constant<int, 32>{});
-  if (K <= 64) return f(std::integral_constant<int, 64>{});
-  return GENRL_EINVAL;
-}
+constexpr int MAX_K = 64;          // classes of a categorical: one per lane of its group (dispatch_w)
 
 }  // namespace
 
@@ -632,6 +621,7 @@ static int onehot_fwd_impl(const float* logits, const float* q, float* sample, f
   if (G <= 0) return GENRL_OK;
   if ((mc.out2 || mc.idx2) && mc.S <= 0) return GENRL_EINVAL;
   if (xo.p && (rowlen <= 0 || xo.ld < rowlen || !xo.inv)) return GENRL_EINVAL;
+  if (K > MAX_K) return GENRL_EINVAL;
   return dispatch_w(K, [&](auto w) {
     constexpr int W = decltype(w)::value;
     hipLaunchKernelGGL((onehot_fwd_kernel<W>), dim3(cdiv(G * W, 256)), dim3(256), 0, (hipStream_t)stream, logits, q,
@@ -662,6 +652,7 @@ static int onehot_bwd_impl(const float* logits, const float* gsample, float* dlo
   if (G <= 0) return GENRL_OK;
   if ((!gsample && !mg.g2) || (mg.g2 && mg.S <= 0)) return GENRL_EINVAL;
   if (xo.p && (rowlen <= 0 || xo.ld < rowlen || !xo.inv || rowlen % K || (G * K) % rowlen)) return GENRL_EINVAL;
+  if (K > MAX_K) return GENRL_EINVAL;
   return dispatch_w(K, [&](auto w) {
     constexpr int W = decltype(w)::value;
     // planes straight from the kernel when a plane row is one workgroup (K == W lanes per group, rowlen a multiple of 64,
@@ -728,6 +719,7 @@ int genrl_cat_kl_fwd(const float* lp, const float* lq, float* kl, float* ent_p, 
                      float unimix, void* stream) {
   GENRL_ENTER();
   if (R <= 0) return GENRL_OK;
+  if (K > MAX_K) return GENRL_EINVAL;
   return dispatch_w(K, [&](auto w) {
     constexpr int W = decltype(w)::value;
     hipLaunchKernelGGL((cat_kl_fwd_kernel<W>), dim3(R), dim3(256), 0, (hipStream_t)stream, lp, lq, kl, ent_p, ent_q, S,
@@ -741,6 +733,7 @@ int genrl_cat_kl_bwd(const float* lp, const float* lq, const float* gp, const fl
                      int S, int K, float unimix, void* stream) {
   GENRL_ENTER();
   if (R <= 0) return GENRL_OK;
+  if (K > MAX_K) return GENRL_EINVAL;
   const long G = R * S;
   return dispatch_w(K, [&](auto w) {
     constexpr int W = decltype(w)::value;

@@ -1,7 +1,7 @@
-// Row kernels of the Plan2Explore ensemble (agent/plan2explore.py:8-41): the ReLU between a member's two products, the row-wise L2
-// prediction error of the training loss and the across-member variance of the intrinsic reward, each with its backward.
+// Row kernels of the Plan2Explore ensemble (agent/plan2explore.py:8-41): the row-wise L2 prediction error of the training loss and the
+// across-member variance of the intrinsic reward, each with its backward.  (The ReLU between a member's two products is in rowact.hip.)
 //
-// All six are HBM-bound streams over rows of up to 12 288 floats (any multiple of 4): one 256-thread workgroup walks rows
+// All four are HBM-bound streams over rows of up to 12 288 floats (any multiple of 4): one 256-thread workgroup walks rows
 // grid-strided with 16-byte accesses.  A kernel that also emits h2 planes needs the row maximum before it can split, so it makes two
 // sweeps over the row: the first computes and stores the fp32 result and takes the maximum, the second re-reads what THIS thread has
 // just stored (the same addresses in program order: served by the L2, the row is <= 48 KiB per member) and writes the planes.  HBM
@@ -14,62 +14,8 @@
 
 namespace {
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 constexpr int ENS_GRID = 2048;          // workgroups at most: rows are grid-strided
 constexpr int ENS_MAXK = 8;
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
-// second sweep: planes of the row this thread has just written
-__device__ __forceinline__ void planes_of_row(const float* yr, int nv, const PlaneOut& xo, long row, float amax, float* red) {
-  const float inv = h2_inv_of(block_max_256(amax, red)), sc = h2_scale_of(inv);
-  for (int j = threadIdx.x; j < nv; j += 256) h2_store4(xo, row, 4 * j, ld4(yr + 4 * j), sc);
-  if (threadIdx.x == 0) xo.inv[row] = inv;
-}
-
-// y = max(x, 0) (y may be x itself)
-__global__ __launch_bounds__(256) void relu_fwd_kernel(const float* x, long ldx, float* y, long ldy, int M, int N, PlaneOut xo) {
-  __shared__ float red[8];
-  const int nv = N >> 2;
-  for (long row = blockIdx.x; row < M; row += gridDim.x) {
-    const float* xr = x + row * ldx;
-    float* yr = y + row * ldy;
-    float am = 0.f;
-    for (int j = threadIdx.x; j < nv; j += 256) {
-      float4 v = ld4(xr + 4 * j);
-      // (a NaN stays NaN, as in torch.relu: fmaxf would drop it)
-      v.x = v.x > 0.f ? v.x : (v.x != v.x ? v.x : 0.f);
-      v.y = v.y > 0.f ? v.y : (v.y != v.y ? v.y : 0.f);
-      v.z = v.z > 0.f ? v.z : (v.z != v.z ? v.z : 0.f);
-      v.w = v.w > 0.f ? v.w : (v.w != v.w ? v.w : 0.f);
-      st4(yr + 4 * j, v);
-      am = fmaxf(am, h2_amax4(v));
-    }
-    if (xo.p) planes_of_row(yr, nv, xo, row, am, red);
-  }
-}
-
-// dx = dy [y > 0] (dx may be dy itself)
-__global__ __launch_bounds__(256) void relu_bwd_kernel(const float* dy, long lddy, const float* y, long ldy, float* dx, long lddx,
-                                                       int M, int N, PlaneOut xo) {
-  __shared__ float red[8];
-  const int nv = N >> 2;
-  for (long row = blockIdx.x; row < M; row += gridDim.x) {
-    const float* gr = dy + row * lddy;
-    const float* yr = y + row * ldy;
-    float* dr = dx + row * lddx;
-    float am = 0.f;
-    for (int j = threadIdx.x; j < nv; j += 256) {
-      const float4 g = ld4(gr + 4 * j), a = ld4(yr + 4 * j);
-      float4 v;
-      v.x = a.x > 0.f ? g.x : 0.f; v.y = a.y > 0.f ? g.y : 0.f; v.z = a.z > 0.f ? g.z : 0.f; v.w = a.w > 0.f ? g.w : 0.f;
-      st4(dr + 4 * j, v);
-      am = fmaxf(am, h2_amax4(v));
-    }
-    if (xo.p) planes_of_row(dr, nv, xo, row, am, red);
-  }
-}
 
 // err[m] = || t[m] - p[m] ||
 __global__ __launch_bounds__(256) void l2err_fwd_kernel(const float* __restrict__ t, long ldt, const float* __restrict__ p, long ldp,
@@ -202,43 +148,16 @@ __global__ __launch_bounds__(256) void ens_var_bwd_kernel(const float* __restric
   }
 }
 
-inline int row_grid(int M) { return M < ENS_GRID ? M : ENS_GRID; }
-inline bool bad_planes(const uint16_t* yp, long ldp, const float* inv, int N) { return yp && (!inv || (ldp & 3) || ldp < N); }
-
 }  // namespace
 
 extern "C" {
-
-int genrl_relu_fwd_h2(const float* x, long ldx, float* y, long ldy, int M, int N, uint16_t* yp, long ldp, long plane, float* inv,
-                      void* stream) {
-  GENRL_ENTER();
-  if (M <= 0) return GENRL_OK;
-  if (N <= 0 || (N & 3) || (ldx & 3) || (ldy & 3) || ldx < N || ldy < N || !x || !y || !aligned16(x) || !aligned16(y) ||
-      bad_planes(yp, ldp, inv, N))
-    return GENRL_EINVAL;
-  relu_fwd_kernel<<<row_grid(M), 256, 0, (hipStream_t)stream>>>(x, ldx, y, ldy, M, N, PlaneOut{yp, ldp, plane, inv});
-  GENRL_CHECK_LAUNCH();
-  return GENRL_OK;
-}
-
-int genrl_relu_bwd_h2(const float* dy, long lddy, const float* y, long ldy, float* dx, long lddx, int M, int N, uint16_t* dxp, long ldp,
-                      long plane, float* inv, void* stream) {
-  GENRL_ENTER();
-  if (M <= 0) return GENRL_OK;
-  if (N <= 0 || (N & 3) || (lddy & 3) || (ldy & 3) || (lddx & 3) || lddy < N || ldy < N || lddx < N || !dy || !y || !dx ||
-      !aligned16(dy) || !aligned16(y) || !aligned16(dx) || bad_planes(dxp, ldp, inv, N))
-    return GENRL_EINVAL;
-  relu_bwd_kernel<<<row_grid(M), 256, 0, (hipStream_t)stream>>>(dy, lddy, y, ldy, dx, lddx, M, N, PlaneOut{dxp, ldp, plane, inv});
-  GENRL_CHECK_LAUNCH();
-  return GENRL_OK;
-}
 
 int genrl_l2err_fwd(const float* t, long ldt, const float* p, long ldp, float* err, int M, int N, void* stream) {
   GENRL_ENTER();
   if (M <= 0) return GENRL_OK;
   if (N <= 0 || (N & 3) || (ldt & 3) || (ldp & 3) || ldt < N || ldp < N || !t || !p || !err || !aligned16(t) || !aligned16(p))
     return GENRL_EINVAL;
-  l2err_fwd_kernel<<<row_grid(M), 256, 0, (hipStream_t)stream>>>(t, ldt, p, ldp, err, M, N);
+  l2err_fwd_kernel<<<row_grid(M, ENS_GRID), 256, 0, (hipStream_t)stream>>>(t, ldt, p, ldp, err, M, N);
   GENRL_CHECK_LAUNCH();
   return GENRL_OK;
 }
@@ -250,20 +169,20 @@ int genrl_l2err_bwd(const float* g, const float* err, const float* t, long ldt, 
   if (N <= 0 || (N & 3) || (ldt & 3) || (ldp & 3) || (lddp & 3) || ldt < N || ldp < N || lddp < N || !g || !err || !t || !p || !dp ||
       !aligned16(t) || !aligned16(p) || !aligned16(dp) || bad_planes(dpp, ldpl, inv, N))
     return GENRL_EINVAL;
-  l2err_bwd_kernel<<<row_grid(M), 256, 0, (hipStream_t)stream>>>(g, err, t, ldt, p, ldp, dp, lddp, M, N, PlaneOut{dpp, ldpl, plane, inv});
+  l2err_bwd_kernel<<<row_grid(M, ENS_GRID), 256, 0, (hipStream_t)stream>>>(g, err, t, ldt, p, ldp, dp, lddp, M, N, PlaneOut{dpp, ldpl, plane, inv});
   GENRL_CHECK_LAUNCH();
   return GENRL_OK;
 }
 
-#define ENS_DISPATCH(KERNEL, ...)                                                                          \
-  switch (K) {                                                                                             \
-    case 2: KERNEL<2><<<row_grid(M), 256, 0, (hipStream_t)stream>>>(__VA_ARGS__); break;                   \
-    case 3: KERNEL<3><<<row_grid(M), 256, 0, (hipStream_t)stream>>>(__VA_ARGS__); break;                   \
-    case 4: KERNEL<4><<<row_grid(M), 256, 0, (hipStream_t)stream>>>(__VA_ARGS__); break;                   \
-    case 5: KERNEL<5><<<row_grid(M), 256, 0, (hipStream_t)stream>>>(__VA_ARGS__); break;                   \
-    case 6: KERNEL<6><<<row_grid(M), 256, 0, (hipStream_t)stream>>>(__VA_ARGS__); break;                   \
-    case 7: KERNEL<7><<<row_grid(M), 256, 0, (hipStream_t)stream>>>(__VA_ARGS__); break;                   \
-    default: KERNEL<8><<<row_grid(M), 256, 0, (hipStream_t)stream>>>(__VA_ARGS__); break;                  \
+#define ENS_DISPATCH(KERNEL, ...)                                                                                     \
+  switch (K) {                                                                                                        \
+    case 2: KERNEL<2><<<row_grid(M, ENS_GRID), 256, 0, (hipStream_t)stream>>>(__VA_ARGS__); break;                    \
+    case 3: KERNEL<3><<<row_grid(M, ENS_GRID), 256, 0, (hipStream_t)stream>>>(__VA_ARGS__); break;                    \
+    case 4: KERNEL<4><<<row_grid(M, ENS_GRID), 256, 0, (hipStream_t)stream>>>(__VA_ARGS__); break;                    \
+    case 5: KERNEL<5><<<row_grid(M, ENS_GRID), 256, 0, (hipStream_t)stream>>>(__VA_ARGS__); break;                    \
+    case 6: KERNEL<6><<<row_grid(M, ENS_GRID), 256, 0, (hipStream_t)stream>>>(__VA_ARGS__); break;                    \
+    case 7: KERNEL<7><<<row_grid(M, ENS_GRID), 256, 0, (hipStream_t)stream>>>(__VA_ARGS__); break;                    \
+    default: KERNEL<8><<<row_grid(M, ENS_GRID), 256, 0, (hipStream_t)stream>>>(__VA_ARGS__); break;                   \
   }
 
 int genrl_ens_var_fwd(const float* p, long member, long ld, int K, float* r, int M, int N, void* stream) {

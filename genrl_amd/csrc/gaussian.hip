@@ -1,29 +1,24 @@
 // Continuous (Gaussian) RSSM latents (gfx950): the sufficient-statistics head of EnsembleRSSM._suff_stats_layer with `discrete: False`
 // (agent/dreamer_utils.py:513-521) fused with the reparameterised sample of get_dist (:416-419), and the Normal-Normal KL of
 // EnsembleRSSM.kl_loss (:534-555; torch's kl_normal_normal under Independent(., 1)) with the entropies of both sides, each with its
-// backward.  Bandwidth-bound row kernels: the head pair walks rows grid-strided with one 256-thread workgroup per row, as the SiLU pair of
-// normfree.hip does, with 16-byte accesses where pointers, S and pitches allow and scalar ones otherwise (the std half of a row starts
+// backward.  Bandwidth-bound row kernels: the head pair walks rows grid-strided with one 256-thread workgroup per row, as the activations of
+// rowact.hip do, with 16-byte accesses where pointers, S and pitches allow and scalar ones otherwise (the std half of a row starts
 // at column S: 8-byte aligned only for S = 30); the KL puts a row on an aligned group of W lanes that stride over S and combine with
 // shuffles in a fixed order, as the categorical kernels of dist.hip / discrete.hip do.  No allocation, no synchronisation with the host,
 // no atomics.
 #include "common.h"
 #include "genrl_hip.h"
 #include <math.h>
-#include <type_traits>
 
 namespace {
 
 constexpr int GS_GRID = 2048;          // workgroups at most: rows are grid-strided
 enum { ACT_SOFTPLUS = 0, ACT_SIGMOID = 1, ACT_SIGMOID2 = 2 };
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
-// the std activation before `+ min_std`.  softplus is torch's (beta 1, threshold 20): x above the threshold, log1p(exp(x)) below
+// the std activation before `+ min_std`
 template <int ACT>
 __device__ __forceinline__ float std_act(float x) {
-  if (ACT == ACT_SOFTPLUS) return x > 20.0f ? x : log1pf(expf(x));
+  if (ACT == ACT_SOFTPLUS) return softplusf_(x);
   if (ACT == ACT_SIGMOID) return sigmoidf_(x);
   return 2.0f * sigmoidf_(0.5f * x);
 }
@@ -124,13 +119,6 @@ __global__ __launch_bounds__(256) void gauss_head_bwd_kernel(const float* __rest
 }
 
 // ---- Normal-Normal KL: one row per aligned group of W lanes; double arithmetic and accumulation, fixed order
-template <int W>
-__device__ __forceinline__ double group_sum_d(double v) {
-#pragma unroll
-  for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // kl[m] = sum_s 0.5 (v + t - 1 - log v), v = (std_l / std_r)^2, t = ((mean_l - mean_r) / std_r)^2;
 // ent_x[m] = sum_s (0.5 + 0.5 log 2 pi + log std_x)   (any output may be null)
 template <int W>
@@ -195,16 +183,6 @@ int dispatch_act(int act, F&& f) {
   return f(std::integral_constant<int, ACT_SIGMOID2>{});
 }
 
-template <typename F>
-int dispatch_w(int S, F&& f) {
-  if (S <= 4) return f(std::integral_constant<int, 4>{});
-  if (S <= 8) return f(std::integral_constant<int, 8>{});
-  if (S <= 16) return f(std::integral_constant<int, 16>{});
-  if (S <= 32) return f(std::integral_constant<int, 32>{});
-  return f(std::integral_constant<int, 64>{});
-}
-
-inline int row_grid(long R) { return R < GS_GRID ? (int)R : GS_GRID; }
 inline bool bad_act(int act) { return act != ACT_SOFTPLUS && act != ACT_SIGMOID && act != ACT_SIGMOID2; }
 inline bool vec_ok(const void* p) { return !p || aligned16(p); }
 constexpr int GS_MAX_S = 1 << 20;
@@ -222,10 +200,10 @@ int genrl_gauss_head_fwd(const float* raw, long ldr, const float* eps, float* me
   return dispatch_act(std_act, [&](auto a) {
     constexpr int ACT = decltype(a)::value;
     if (vec)
-      hipLaunchKernelGGL((gauss_head_fwd_kernel<ACT, true>), dim3(row_grid(R)), dim3(256), 0, (hipStream_t)stream, raw, ldr, eps, mean,
+      hipLaunchKernelGGL((gauss_head_fwd_kernel<ACT, true>), dim3(row_grid(R, GS_GRID)), dim3(256), 0, (hipStream_t)stream, raw, ldr, eps, mean,
                          std, stoch, R, S, min_std);
     else
-      hipLaunchKernelGGL((gauss_head_fwd_kernel<ACT, false>), dim3(row_grid(R)), dim3(256), 0, (hipStream_t)stream, raw, ldr, eps, mean,
+      hipLaunchKernelGGL((gauss_head_fwd_kernel<ACT, false>), dim3(row_grid(R, GS_GRID)), dim3(256), 0, (hipStream_t)stream, raw, ldr, eps, mean,
                          std, stoch, R, S, min_std);
     GENRL_CHECK_LAUNCH();
     return GENRL_OK;
@@ -244,10 +222,10 @@ int genrl_gauss_head_bwd(const float* dstoch, const float* dmean, const float* d
   return dispatch_act(std_act, [&](auto a) {
     constexpr int ACT = decltype(a)::value;
     if (vec)
-      hipLaunchKernelGGL((gauss_head_bwd_kernel<ACT, true>), dim3(row_grid(R)), dim3(256), 0, (hipStream_t)stream, dstoch, dmean, dstd,
+      hipLaunchKernelGGL((gauss_head_bwd_kernel<ACT, true>), dim3(row_grid(R, GS_GRID)), dim3(256), 0, (hipStream_t)stream, dstoch, dmean, dstd,
                          raw, ldr, eps, draw, lddr, R, S, accumulate);
     else
-      hipLaunchKernelGGL((gauss_head_bwd_kernel<ACT, false>), dim3(row_grid(R)), dim3(256), 0, (hipStream_t)stream, dstoch, dmean, dstd,
+      hipLaunchKernelGGL((gauss_head_bwd_kernel<ACT, false>), dim3(row_grid(R, GS_GRID)), dim3(256), 0, (hipStream_t)stream, dstoch, dmean, dstd,
                          raw, ldr, eps, draw, lddr, R, S, accumulate);
     GENRL_CHECK_LAUNCH();
     return GENRL_OK;

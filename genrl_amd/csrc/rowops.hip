@@ -1,9 +1,9 @@
 // Row-wise fused kernels of the GenRL hot path (gfx950): LayerNorm(+SiLU) (dense layers and, on
-// NHWC activations, the image channel-LayerNorm), the GRU gate block, the actor's Normal head,
-// column reductions and small copies.
+// NHWC activations, the image channel-LayerNorm), the GRU gate block, the actor's output layer fused
+// with its Normal head, column reductions and small copies.
 // All are HBM/L2-bound: one 64-lane wave owns one row, lanes stride the row so every global
 // access is a coalesced 256-B segment, reductions are wavefront shuffles (no LDS).
-#include "common.h"
+#include "actor_heads.h"
 #include "genrl_hip.h"
 #include <algorithm>
 
@@ -411,48 +411,7 @@ __global__ __launch_bounds__(256) void colsum_narrow_kernel(const float* __restr
   }
 }
 
-// ------------------------------------------------------------------ actor Normal head
-// raw[R,2A] = [out | std_raw]; mean = tanh(out); std = (max-min)*sigmoid(std_raw+2)+min;
-// action = mean + std*eps.   ref: DistLayer 'normal', agent/dreamer_utils.py:814-819
-__global__ void actor_head_fwd_kernel(const float* __restrict__ raw, const float* __restrict__ eps,
-                                      float* __restrict__ action, float* __restrict__ mean_out,
-                                      float* __restrict__ std_out, long n, int A, float min_std,
-                                      float max_std, long ld_action) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const long r = i / A;
-  const int a = (int)(i % A);
-  const float mean = tanhf(raw[r * 2 * A + a]);
-  const float sd = (max_std - min_std) * sigmoidf_(raw[r * 2 * A + A + a] + 2.0f) + min_std;
-  const float act = mean + sd * (eps ? eps[i] : 0.f);
-  if (action) action[r * ld_action + a] = act;
-  if (mean_out) mean_out[i] = mean;
-  if (std_out) std_out[i] = sd;
-}
-
-// the same with an h2-plane copy of the action rows: one thread per row (A ~ 10: the row maximum is a loop)
-__global__ void actor_head_fwd_rows_kernel(const float* __restrict__ raw, const float* __restrict__ eps,
-                                           float* __restrict__ action, float* __restrict__ mean_out,
-                                           float* __restrict__ std_out, long R, int A, float min_std,
-                                           float max_std, long ld_action, PlaneOut xo) {
-  const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= R) return;
-  float amax = 0.f;
-  for (int a = 0; a < A; ++a) {
-    const float mean = tanhf(raw[r * 2 * A + a]);
-    const float sd = (max_std - min_std) * sigmoidf_(raw[r * 2 * A + A + a] + 2.0f) + min_std;
-    const float act = mean + sd * (eps ? eps[r * A + a] : 0.f);
-    amax = fmaxf(amax, fabsf(act));
-    action[r * ld_action + a] = act;
-    if (mean_out) mean_out[r * A + a] = mean;
-    if (std_out) std_out[r * A + a] = sd;
-  }
-  const float inv = h2_inv_of(amax), sc = h2_scale_of(inv);
-  xo.inv[r] = inv;
-  for (int a = 0; a < A; ++a) h2_store1(xo, r * xo.ld + a, action[r * ld_action + a], sc);
-}
-
-
+// ------------------------------------------------------------------ actor Normal head fused with the output layer
 // fp32 -> nearest-even bf16 -> fp32 (finite inputs), componentwise
 __device__ __forceinline__ float bf16r(float x) {
   const unsigned u = __builtin_bit_cast(unsigned, x);
@@ -514,9 +473,7 @@ __global__ __launch_bounds__(256) void actor_head_linear_fwd_kernel(const float*
   out_s = __shfl(out_o, min(lane + A, 63), 64);          // lane a < A: std_raw[a] sits in lane A + a (A <= 32)
   float act = 0.f;
   if (lane < A) {
-    const float mean = tanhf(out_o);
-    const float sd = (max_std - min_std) * sigmoidf_(out_s + 2.0f) + min_std;
-    act = mean + sd * (eps ? eps[row * A + lane] : 0.f);
+    act = NormalHead(out_o, out_s, min_std, max_std).action(eps ? eps[row * A + lane] : 0.f, eps != nullptr);
     action[row * ld_action + lane] = act;
   }
   if (xo.p) {
@@ -569,24 +526,8 @@ __global__ __launch_bounds__(256) void actor_head_linear_bwd_kernel(const float*
   if (wave != 0 || lane >= A) return;
   float g = part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane];
   if (daction_up) g += daction_up[row * ld_action + lane];
-  const float mean = tanhf(raw[row * 2 * A + lane]);
-  const float sg = sigmoidf_(raw[row * 2 * A + A + lane] + 2.0f);
-  draw[row * 2 * A + lane] = g * (1.0f - mean * mean);
-  draw[row * 2 * A + A + lane] = g * eps[row * A + lane] * (max_std - min_std) * sg * (1.0f - sg);
-}
-
-__global__ void actor_head_bwd_kernel(const float* __restrict__ daction, const float* __restrict__ raw,
-                                      const float* __restrict__ eps, float* __restrict__ draw, long n, int A,
-                                      float min_std, float max_std, long ld_action) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const long r = i / A;
-  const int a = (int)(i % A);
-  const float mean = tanhf(raw[r * 2 * A + a]);
-  const float sg = sigmoidf_(raw[r * 2 * A + A + a] + 2.0f);
-  const float g = daction[r * ld_action + a];
-  draw[r * 2 * A + a] = g * (1.0f - mean * mean);
-  draw[r * 2 * A + A + a] = g * eps[i] * (max_std - min_std) * sg * (1.0f - sg);
+  const NormalHead h(raw[row * 2 * A + lane], raw[row * 2 * A + A + lane], min_std, max_std);
+  h.backward(g, eps[row * A + lane], draw[row * 2 * A + lane], draw[row * 2 * A + A + lane]);
 }
 
 // ------------------------------------------------------------------ strided 2-D copy / scale
@@ -1309,7 +1250,6 @@ __global__ __launch_bounds__(256) void gru_gates_bwd_blk_kernel(
   }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 constexpr int BLK_GRID = 512;   // workgroups of the block-per-row FORWARD kernels (x 4); rows are grid-strided
 // the backward kernels (one partial row of parameter gradients per workgroup): GENRL_BLK_GRID, see blk_grid_for
 
@@ -1756,32 +1696,7 @@ int genrl_gru_gates_bwd_ldp(const float* dhout, long lddo, const float* dhout2, 
                             PlaneOut{nullptr, 0, 0, nullptr}, stream, ldpart);
 }
 
-static int actor_head_fwd_impl(const float* raw, const float* eps, float* action, float* mean, float* std, long R, int A,
-                         float min_std, float max_std, long ld_action, PlaneOut xo, void* stream) {
-  GENRL_ENTER();
-  const long n = R * A;
-  if (n <= 0) return GENRL_OK;
-  if (xo.p && (xo.ld < A || !xo.inv || !action)) return GENRL_EINVAL;
-  if (xo.p)
-    hipLaunchKernelGGL(actor_head_fwd_rows_kernel, dim3(cdiv(R, 64)), dim3(64), 0, (hipStream_t)stream, raw, eps, action,
-                       mean, std, R, A, min_std, max_std, ld_action > 0 ? ld_action : (long)A, xo);
-  else
-    hipLaunchKernelGGL(actor_head_fwd_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, raw, eps, action,
-                       mean, std, n, A, min_std, max_std, ld_action > 0 ? ld_action : (long)A);
-  GENRL_CHECK_LAUNCH();
-  return GENRL_OK;
-}
-int genrl_actor_head_fwd(const float* raw, const float* eps, float* action, float* mean, float* std, long R, int A,
-                         float min_std, float max_std, long ld_action, void* stream) {
-  return actor_head_fwd_impl(raw, eps, action, mean, std, R, A, min_std, max_std, ld_action, PlaneOut{nullptr, 0, 0, nullptr}, stream);
-}
-/* + the action as x3 planes (rows ldp wide; the columns >= A must have been zeroed by the caller once) */
-int genrl_actor_head_fwd_h2(const float* raw, const float* eps, float* action, float* mean, float* std, long R, int A,
-                            float min_std, float max_std, long ld_action, uint16_t* ap, long ldp, long plane, float* inv, void* stream) {
-  return actor_head_fwd_impl(raw, eps, action, mean, std, R, A, min_std, max_std, ld_action, PlaneOut{ap, ldp, plane, inv}, stream);
-}
-
-/* out = y W^T + b (W: 2A x U, row-major) followed by the head above: raw (R x 2A) and action (R x ld_action) are written,
+/* out = y W^T + b (W: 2A x U, row-major) followed by the Normal head (actor_heads.h): raw (R x 2A) and action (R x ld_action) are written,
  * optionally the action's h2 planes (ap != NULL).  U % 4 == 0, A <= 32, 16-byte aligned y rows and W. */
 static int actor_head_linear_fwd_impl(const float* y, long ldy, const float* W, const float* b, const float* eps, float* raw,
                                       float* action, long R, int U, int A, float min_std, float max_std, long ld_action, uint16_t* ap,
@@ -1824,17 +1739,6 @@ int genrl_actor_head_linear_bwd(const float* dx, long lddx, const float* WaT, co
 #define GO(MO) hipLaunchKernelGGL((actor_head_linear_bwd_kernel<MO>), grid, block, 0, s, dx, lddx, WaT, daction_up, ld_action, raw, eps, draw, R, U, A, min_std, max_std, (int)(genrl_gemm_precision() == 1))
   if (A <= 6) GO(6); else if (A <= 10) GO(10); else if (A <= 16) GO(16); else GO(32);
 #undef GO
-  GENRL_CHECK_LAUNCH();
-  return GENRL_OK;
-}
-
-int genrl_actor_head_bwd(const float* daction, const float* raw, const float* eps, float* draw, long R, int A,
-                         float min_std, float max_std, long ld_action, void* stream) {
-  GENRL_ENTER();
-  const long n = R * A;
-  if (n <= 0) return GENRL_OK;
-  hipLaunchKernelGGL(actor_head_bwd_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, daction, raw, eps,
-                     draw, n, A, min_std, max_std, ld_action > 0 ? ld_action : (long)A);
   GENRL_CHECK_LAUNCH();
   return GENRL_OK;
 }

@@ -3,26 +3,13 @@
 // return-normalised actor objective (agent/dreamer.py:392-429), weighted means of per-row losses (:431-438, :229-243)
 // and the policy-entropy metric -- as one launch each.  All are reductions over <= a few 10^5 floats (H x N returns):
 // one workgroup of 1024 threads, fixed summation order (deterministic), double accumulation.
-#include "common.h"
+#include "actor_heads.h"
 #include <algorithm>
 #include <math.h>
 
 namespace {
 
 constexpr int NT = 1024;
-
-__device__ __forceinline__ double block_sum_d(double v, double* red /* 16 doubles */) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  __syncthreads();
-  if (l == 0) red[w] = v;
-  __syncthreads();
-  double r = 0.0;
-#pragma unroll
-  for (int i = 0; i < NT / 64; ++i) r += red[i];
-  return r;
-}
 
 // out[0..3] = mean, unbiased std, mean |x|, mean x^2
 __global__ __launch_bounds__(NT) void moments_kernel(const float* __restrict__ x, long n, float* __restrict__ out) {
@@ -187,7 +174,7 @@ __global__ void actor_obj_bwd_kernel(const float* __restrict__ g, const float* _
   dtarget[i] = i < N ? 0.f : -g[0] * (weight ? weight[i - N] : 1.0f) / (os[1] * (float)((double)(H - 1) * N));
 }
 
-// mean over rows of the entropy of Independent(Normal(., std)): std = (max-min) sigmoid(raw_std + 2) + min.  Two stages with a
+// mean over rows of the entropy of Independent(Normal(., std)), std the Normal head's (actor_heads.h).  Two stages with a
 // fixed order: one thread per row, one partial per workgroup (double), then one workgroup sums the partials.
 __global__ __launch_bounds__(256) void normal_entropy_part_kernel(const float* __restrict__ raw, long R, int A, float min_std,
                                                                   float max_std, double* __restrict__ part) {
@@ -195,7 +182,7 @@ __global__ __launch_bounds__(256) void normal_entropy_part_kernel(const float* _
   double s = 0.0;
   for (long r = (long)blockIdx.x * 256 + threadIdx.x; r < R; r += (long)gridDim.x * 256) {
     float t = 0.f;
-    for (int a = 0; a < A; ++a) t += logf((max_std - min_std) * sigmoidf_(raw[r * 2 * A + A + a] + 2.0f) + min_std);
+    for (int a = 0; a < A; ++a) t += logf(NormalHead(0.f, raw[r * 2 * A + A + a], min_std, max_std).std);      // (out: not in the entropy)
     s += A * (0.5 + 0.5 * log(2.0 * M_PI)) + (double)t;
   }
 #pragma unroll

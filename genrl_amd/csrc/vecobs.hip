@@ -1,26 +1,19 @@
 // Vector (1-D) observations (gfx950): the symlog of the encoder's MLP inputs (agent/dreamer_utils.py:623-628, `symlog_inputs`) written
 // straight into a column slice of the first layer's input, so that the concatenation of several keys is one launch per key and no copy;
-// and the log-likelihood of the decoder's vector heads with its gradient -- MSEDist on a D-wide head (:62-83) and SymlogDist 'mse' with
-// agg 'sum' (:85-118, `mlp_dist: symlog_mse`).  Bandwidth-bound row kernels: the symlog walks the elements flat, with 16-byte accesses where
-// pointers, D and pitches allow and scalar ones otherwise (widths such as 7 and 9 are the normal case); the likelihood puts a row on an
-// aligned group of W lanes that stride over D and combine with shuffles in a fixed order, as gauss_kl_fwd_kernel of gaussian.hip does; its
-// gradient is elementwise.  No allocation, no synchronisation with the host, no atomics.
+// and the log-likelihood of the decoder's vector heads with its gradient -- MSEDist on a D-wide head (:62-83), with the elementwise
+// squared error of the one-wide `mse` heads (reward, critic) as a pair of its own, and SymlogDist 'mse' with agg 'sum' (:85-118,
+// `mlp_dist: symlog_mse`).  Bandwidth-bound row kernels: the symlog walks the elements flat, with 16-byte accesses where pointers, D and
+// pitches allow and scalar ones otherwise (widths such as 7 and 9 are the normal case); the likelihood puts a row on an aligned group of W
+// lanes that stride over D and combine with shuffles in a fixed order, as gauss_kl_fwd_kernel of gaussian.hip does; its gradient is
+// elementwise.  No allocation, no synchronisation with the host, no atomics.
 #include "common.h"
 #include "genrl_hip.h"
 #include <math.h>
-#include <type_traits>
 
 namespace {
 
 constexpr int VO_GRID = 1 << 16;       // workgroups at most: elements are grid-strided
 constexpr int VO_MAX_D = 1 << 20;
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
-// sign(x) log(|x| + 1) as dist.hip's symlogf_: |x| + 1 is rounded to fp32 first, as the reference and the oracle do (no log1p)
-__device__ __forceinline__ float symlogf_(float x) { return copysignf(logf(fabsf(x) + 1.0f), x); }
 
 template <bool SYMLOG>
 __device__ __forceinline__ float maybe_symlog(float x) { return SYMLOG ? symlogf_(x) : x; }
@@ -42,13 +35,6 @@ __global__ __launch_bounds__(256) void symlog_rows_kernel(const float* __restric
       y[row * ldy + c] = maybe_symlog<SYMLOG>(x[row * ldx + c]);
     }
   }
-}
-
-template <int W>
-__device__ __forceinline__ double group_sum_d(double v) {
-#pragma unroll
-  for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // one element's distance: (mode - t)^2 in double from the fp32 operands, t = x or symlog(x) -- the logarithm in double as well: the target
@@ -95,13 +81,20 @@ __global__ __launch_bounds__(256) void vec_like_bwd_kernel(const float* __restri
   }
 }
 
-template <typename F>
-int dispatch_w(int D, F&& f) {
-  if (D <= 4) return f(std::integral_constant<int, 4>{});
-  if (D <= 8) return f(std::integral_constant<int, 8>{});
-  if (D <= 16) return f(std::integral_constant<int, 16>{});
-  if (D <= 32) return f(std::integral_constant<int, 32>{});
-  return f(std::integral_constant<int, 64>{});
+// the one-wide heads, on contiguous operands and in fp32: like = -(out - x)^2 per element
+__global__ void sqerr_fwd_kernel(const float* __restrict__ out, const float* __restrict__ x, float* __restrict__ like, long n) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float d = out[i] - x[i];
+  like[i] = -(d * d);
+}
+
+// dout = -2 (out - x) g
+__global__ void sqerr_bwd_kernel(const float* __restrict__ out, const float* __restrict__ x, const float* __restrict__ g,
+                                 float* __restrict__ dout, long n) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  dout[i] = -2.0f * (out[i] - x[i]) * g[i];
 }
 
 inline int flat_grid(long n) {
@@ -164,6 +157,24 @@ int genrl_vec_like_bwd(const float* mode, long ldm, const float* x, long ldx, co
   else
     hipLaunchKernelGGL((vec_like_bwd_kernel<1>), grid, block, 0, (hipStream_t)stream, mode, ldm, x, ldx, g, dmode, lddm, R, D, tol,
                        accumulate);
+  GENRL_CHECK_LAUNCH();
+  return GENRL_OK;
+}
+
+int genrl_sqerr_fwd(const float* out, const float* x, float* like, long n, void* stream) {
+  GENRL_ENTER();
+  if (n <= 0) return GENRL_OK;
+  if (!out || !x || !like) return GENRL_EINVAL;
+  sqerr_fwd_kernel<<<cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(out, x, like, n);
+  GENRL_CHECK_LAUNCH();
+  return GENRL_OK;
+}
+
+int genrl_sqerr_bwd(const float* out, const float* x, const float* g, float* dout, long n, void* stream) {
+  GENRL_ENTER();
+  if (n <= 0) return GENRL_OK;
+  if (!out || !x || !g || !dout) return GENRL_EINVAL;
+  sqerr_bwd_kernel<<<cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(out, x, g, dout, n);
   GENRL_CHECK_LAUNCH();
   return GENRL_OK;
 }

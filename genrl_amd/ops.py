@@ -1045,7 +1045,7 @@ def trunc_normal_mean_std(raw, min_std=0.1, init_std=0.0):
     return _actor_mean_std(raw, _TRUNC_HEAD, min_std, init_std)
 
 
-# ---- the squashed-Gaussian head (squashed.hip): DistLayer 'tanh_normal', SquashedNormal in SampleDist
+# ---- the squashed-Gaussian head (heads.hip): DistLayer 'tanh_normal', SquashedNormal in SampleDist
 
 def tanh_normal_sample(raw, eps, min_std=0.1, init_std=0.0):
     """raw (..., 2A) = [out | std_raw] -> tanh(mean + std eps), mean = 5 tanh(out / 5), std = softplus(std_raw + init_std) + min_std:
@@ -2398,7 +2398,7 @@ def rssm_imagine_seq(act, stoch0, deter0, q, S, K, W_in, b_in, g_in, be_in, W_g,
     return deter, plog, pst
 
 
-# ------------------------------------------------------------------ Plan2Explore ensemble row kernels (csrc/ensemble.hip)
+# ------------------------------------------------------------------ Plan2Explore ensemble row kernels (csrc/ensemble.hip, csrc/rowact.hip)
 
 def _plane_out(P, row0=0):
     """(planes, ld, plane stride, inv) arguments of a row kernel's optional plane output (P: planes.Planes or None)"""
@@ -2505,7 +2505,7 @@ def ens_var(preds):
     return _EnsVar.apply(preds)
 
 
-# ------------------------------------------------------------------ the DreamerV2 defaults (csrc/normfree.hip): norm-free layers, truncated-normal actor, mse heads
+# ------------------------------------------------------------------ the DreamerV2 defaults (csrc/rowact.hip, heads.hip, vecobs.hip): norm-free layers, truncated-normal actor, mse heads
 
 def silu_fwd_raw(x, y, M, N, P=None):
     """y = x sigmoid(x) over M contiguous rows of N floats (y may be x); P: planes of y"""

@@ -626,7 +626,7 @@ int genrl_adam_step(float* p, float* g, float* m, float* v, long n, const float*
                     void* stream);
 int genrl_scale(float* p, long n, float s, void* stream);
 
-/* ---- Plan2Explore ensemble (agent/plan2explore.py:8-41; genrl_amd/csrc/ensemble.hip): the row kernels around a member's two products.
+/* ---- Plan2Explore ensemble (agent/plan2explore.py:8-41; genrl_amd/csrc/ensemble.hip, the ReLU in rowact.hip): the row kernels around a member's two products.
  * Rows of N floats, N % 4 == 0 (tested to 12 288), any row pitch that is a multiple of 4 floats, 16-byte aligned bases; returns 1 otherwise.
  * Plane outputs (yp / dxp / dpp; NULL: none) follow the contract of genrl_ln_act_fwd_h2: planes [.][ldp] `plane` elements apart, inv[row],
  * the row maximum taken over the kernel's output row, columns beyond N untouched -- bit-identical to genrl_split_h2 of the fp32 output.
@@ -646,7 +646,7 @@ int genrl_ens_var_fwd(const float* p, long member, long ld, int K, float* r, int
 int genrl_ens_var_bwd(const float* g, const float* p, long member, long ld, int K, float* dp, long dmember, long lddp, int M, int N,
                       uint16_t* dpp, long pmember, long ldpl, long plane, float* inv, long imember, void* stream);
 
-/* ---- the DreamerV2 defaults (conf/defaults/dreamer_v2.yaml; genrl_amd/csrc/normfree.hip)
+/* ---- the DreamerV2 defaults (conf/defaults/dreamer_v2.yaml; genrl_amd/csrc/rowact.hip, heads.hip, vecobs.hip)
  * genrl_silu_{fwd,bwd}_h2: the activation behind a Linear without LayerNorm (`norm: none`, agent/dreamer_utils.py:739-747).  Rows, pitches,
  *   alignment and the optional plane output as genrl_relu_*_h2 above (planes bit-identical to genrl_split_h2 of the fp32 output).
  *   fwd: y = x sigmoid(x) (y may be x).  bwd: dx = dy sigmoid(x) (1 + x (1 - sigmoid(x))) from the saved pre-activation x (dx may be dy).
@@ -668,7 +668,7 @@ int genrl_sqerr_fwd(const float* out, const float* x, float* like, long n, void*
 int genrl_sqerr_bwd(const float* out, const float* x, const float* g, float* dout, long n, void* stream);
 
 /* ---- the squashed-Gaussian actor head (DistLayer 'tanh_normal', agent/dreamer_utils.py:824-829: SquashedNormal, tools/utils.py:126-170, in
- * SampleDist, agent/dreamer_utils.py:28-60; genrl_amd/csrc/squashed.hip).  raw [R, 2A] = [out | std_raw], 1 <= A <= 64:
+ * SampleDist, agent/dreamer_utils.py:28-60; genrl_amd/csrc/heads.hip).  raw [R, 2A] = [out | std_raw], 1 <= A <= 64:
  *   mean = 5 tanh(out / 5), std = softplus(std_raw + init_std) + min_std (torch's softplus: the identity above 20), x = mean + std eps,
  *   action = tanh(x).  Every entry returns 1 before any launch, and writes nothing, for A out of range, K < 1, a missing required pointer
  *   or no output at all; R = 0 is a no-op.  No NaN or inf for any finite input (out = +-50, std_raw = 25 or -30, eps = +-6, x < -10).

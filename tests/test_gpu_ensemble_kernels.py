@@ -1,4 +1,4 @@
-"""The row kernels of the Plan2Explore ensemble (csrc/ensemble.hip) through their C entry points, with padded row pitches.
+"""The row kernels of the Plan2Explore ensemble (csrc/ensemble.hip, the ReLU of csrc/rowact.hip) through their C entry points, with padded row pitches.
 
 ReLU forward / backward: bit-identical to torch, planes bit-identical to planes.split of the fp32 output.
 l2err and ens_var, forward and backward: error against float64, bounded per case by 2x the error the float32 CPU restatement of the

@@ -1,4 +1,4 @@
-"""The squashed-Gaussian head kernels (csrc/squashed.hip) through their C entry points, under the convention of test_gpu_gauss_kernels.py:
+"""The squashed-Gaussian head kernels (csrc/heads.hip) through their C entry points, under the convention of test_gpu_gauss_kernels.py:
 error against float64, bounded per case by 2x the error the float32 CPU restatement (tests/tanh_restatement.py, plain torch) makes against
 float64 on the same inputs, with a floor of 4 units of 2^-24 x scale.  The factor 2 covers a different evaluation order; the yardstick is the
 restatement, never the kernel.  Outputs are NaN-prefilled inside PAD-filled buffers with a guard row (and padding columns where the output is

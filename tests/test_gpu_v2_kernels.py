@@ -1,4 +1,4 @@
-"""The kernels of the DreamerV2 defaults (csrc/normfree.hip) and the dense_act nodes built on them, against float64.
+"""The kernels of the DreamerV2 defaults (csrc/rowact.hip, heads.hip, vecobs.hip) and the dense_act nodes built on them, against float64.
 
 SiLU pair and truncated-normal head: |kernel - float64| <= max(2 x the worst ratio of the float32 CPU restatement of the same formula
 (tests/v2_restatement.py, autograd for the backward), FLOOR) x 2^-24 x scale per element, the bound of test_gpu_ensemble_kernels.py.  scale
