@@ -446,6 +446,13 @@ class ActorCritic(Module):  # ref :323-462
         # the slow critic is never trained: no wgrad for it (drops the reference's waste)
         self._target_critic.requires_grad_(False)
 
+    def __getstate__(self):
+        """A pickled agent (train.py's checkpoint) belongs to no GraphedStep: the copy advances its slow critic itself again, until a
+        GraphedStep built on it takes that over.  (With the flag saved, a run resumed with eager steps never copied the slow critic.)"""
+        state = dict(self.__dict__)
+        state.pop('_defer_slow_target', None)
+        return state
+
     def update(self, world_model, start, is_terminal, reward_fn):  # ref :366-390
         metrics = {}
         hor = self.cfg.imag_horizon
