@@ -1134,7 +1134,6 @@ class Optimizer:
             raise
         ops.direct_grads = False
         ops.defer_flush()              # one launch sums them all (the backward pass's streams have been joined by autograd)
-        ops.wgrad_stream.join()
         if Optimizer.grad_hook is not None:
             Optimizer.grad_hook(self._name, live)
         if flush_pending:

@@ -222,38 +222,6 @@ def _ln_param_targets(M, N, gamma, beta, bias, dev, need=True, bias_optional=Fal
     return g0, g1, g2, ws, (1 | defer_reduce(M, N, ws, g0, g1, g2)) if direct else 0, direct
 
 
-class _WgradStream:
-    """Weight-gradient GEMMs are off the critical path of backpropagation (nothing downstream in
-    the backward pass reads dW) and accumulate into persistent buffers: when enabled they are
-    enqueued on a side stream so that they run beside the dgrad chain (two GEMM kernels per CU =
-    two independent workgroups, and their fixed launch/prologue/epilogue costs overlap).  The
-    optimiser joins the stream before it reads the gradients.  Operands are kept referenced until
-    the join so the caching allocator cannot recycle them under the side stream.
-    Measured on MI355X (round 1): no gain over in-order launches (49.65 vs 49.70 ms/step) and the
-    fork-per-GEMM pattern does not survive hipGraph capture, so it stays disabled."""
-    enabled = False
-    keep = []
-
-    @classmethod
-    def run(cls, fn, *tensors):
-        if not cls.enabled:
-            return fn()
-        from . import streams
-        cls.keep.extend(tensors)
-        with streams.fork('wgrad'):
-            fn()
-
-    @classmethod
-    def join(cls):
-        if cls.keep:
-            from . import streams
-            streams.join('wgrad')
-            cls.keep.clear()
-
-
-wgrad_stream = _WgradStream
-
-
 def _ws(n, dev):
     return torch.empty(max(int(n), 1), dtype=torch.float32, device=dev)
 
@@ -389,11 +357,7 @@ class _Linear(Function):
             dx = dx.reshape(ctx.xshape)
         if ctx.needs_input_grad[1]:
             tgt, acc, dW = _wgrad_target(W)
-            wg = lambda: sgemm(dy2, 1, ldy, x2, 1, K, tgt, K, None, N, K, M, accumulate=acc)     # dW = dy^T x
-            if acc:
-                wgrad_stream.run(wg, dy2, x2)
-            else:
-                wg()
+            sgemm(dy2, 1, ldy, x2, 1, K, tgt, K, None, N, K, M, accumulate=acc)     # dW = dy^T x
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = _bias_grad(ctx.bias, dy2, ldy)
         return dx, dW, db
@@ -1781,54 +1745,47 @@ def _aligned_block(W, K1, M):
     return W, K
 
 
-class _Linear2(Function):
-    """y = [x1, x2] W^T + b without materialising the concatenation: W = [W1 | W2] column blocks
-    (torch.cat([stoch, action]) -> _img_in, agent/dreamer_utils.py:461-462; feat -> MLP dense0)."""
-    @staticmethod
-    def forward(ctx, x1, x2, W, b):
-        a = _f32(x1).reshape(-1, x1.shape[-1]).contiguous()
-        c = _f32(x2).reshape(-1, x2.shape[-1]).contiguous()
-        M, K1 = a.shape
+def _dense2_fwd(a, c, W, b, pre):
+    """the forward product of a dense layer on [a, c] without the concatenation, W = [W1 | W2] column blocks: pre (M, N) = a W1^T (+ b),
+    += c W2^T when c is given -> (w1, ld1): the first block as the product read it (_aligned_block), for _dense2_dgrad"""
+    M, K1 = a.shape
+    N, K = W.shape
+    w1, ld1 = _aligned_block(W, K1, M)
+    sgemm(a, K1, 1, w1, ld1, 1, pre, N, b, M, N, K1)
+    if c is not None:
         K2 = c.shape[1]
-        N, K = W.shape
-        assert K == K1 + K2 and c.shape[0] == M
-        y = torch.empty(M, N, device=a.device)
-        w1, ld1 = _aligned_block(W, K1, M)
-        sgemm(a, K1, 1, w1, ld1, 1, y, N, b, M, N, K1)
-        sgemm(c, K2, 1, W, K, 1, y, N, None, M, N, K2, accumulate=True, b_off=K1)
-        ctx.w1 = (w1, ld1)
-        ctx.save_for_backward(a, c, W)
-        ctx.has_bias = b is not None
-        ctx.shapes = (x1.shape, x2.shape)
-        return y.reshape(*x1.shape[:-1], N)
+        sgemm(c, K2, 1, W, K, 1, pre, N, None, M, N, K2, accumulate=True, b_off=K1)
+    return w1, ld1
 
-    @staticmethod
-    def backward(ctx, dy):
-        a, c, W = ctx.saved_tensors
-        M, K1 = a.shape
+
+def _dense2_dgrad(dpre, W, w1, K1, K2, need1, need2):
+    """-> (d1, d2) = dpre W1 (M, K1), dpre W2 (M, K2); None where not needed.  w1: _dense2_fwd's (w1, ld1)"""
+    M, N = dpre.shape
+    d1 = d2 = None
+    if need1:
+        d1 = torch.empty(M, K1, device=dpre.device)
+        sgemm(dpre, N, 1, w1[0], 1, w1[1], d1, K1, None, M, K1, N)
+    if need2:
+        d2 = torch.empty(M, K2, device=dpre.device)
+        sgemm(dpre, N, 1, W, 1, W.shape[1], d2, K2, None, M, K2, N, b_off=K1)
+    return d1, d2
+
+
+def _as(d, shape):
+    """an input gradient in the shape its input came in (None stays None)"""
+    return d.reshape(shape) if d is not None else None
+
+
+def _dense2_wgrad(dpre, a, c, W):
+    """dW = dpre^T [a, c] (c may be None), written or added where _wgrad_target says -> what the node returns to autograd for W"""
+    M, K1 = a.shape
+    N, K = W.shape
+    tgt, acc, dW = _wgrad_target(W)
+    sgemm(dpre, 1, N, a, 1, K1, tgt, K, None, N, K1, M, accumulate=acc)
+    if c is not None:
         K2 = c.shape[1]
-        N, K = W.shape
-        dy2 = dy.reshape(M, N).contiguous()
-        d1 = d2 = dW = db = None
-        if ctx.needs_input_grad[0]:
-            d1 = torch.empty(M, K1, device=dy.device)
-            sgemm(dy2, N, 1, ctx.w1[0], 1, ctx.w1[1], d1, K1, None, M, K1, N)
-            d1 = d1.reshape(ctx.shapes[0])
-        if ctx.needs_input_grad[1]:
-            d2 = torch.empty(M, K2, device=dy.device)
-            sgemm(dy2, N, 1, W, 1, K, d2, K2, None, M, K2, N, b_off=K1)
-            d2 = d2.reshape(ctx.shapes[1])
-        if ctx.needs_input_grad[2]:
-            dW = torch.empty(N, K, device=dy.device)
-            sgemm(dy2, 1, N, a, 1, K1, dW, K, None, N, K1, M)
-            sgemm(dy2, 1, N, c, 1, K2, dW, K, None, N, K2, M, c_off=K1)
-        if ctx.has_bias and ctx.needs_input_grad[3]:
-            db = colsum(dy2)
-        return d1, d2, dW, db
-
-
-def linear2(x1, x2, W, b=None):
-    return _Linear2.apply(x1, x2, W, b)
+        sgemm(dpre, 1, N, c, 1, K2, tgt, K, None, N, K2, M, accumulate=acc, c_off=K1)
+    return dW
 
 
 class _GRUStep(Function):
@@ -1874,14 +1831,7 @@ class _GRUStep(Function):
         else:
             dh = None
         if ctx.needs_input_grad[2]:
-            tgt, acc, dW = _wgrad_target(W)
-            def wg():
-                sgemm(dpre, 1, 3 * D, x, 1, I, tgt, K, None, 3 * D, I, R, accumulate=acc)
-                sgemm(dpre, 1, 3 * D, h, 1, D, tgt, K, None, 3 * D, D, R, accumulate=acc, c_off=I)
-            if acc:
-                wgrad_stream.run(wg, dpre, x, h)
-            else:
-                wg()
+            dW = _dense2_wgrad(dpre, x, h, W)
         if need_p and not direct:
             return dx, dh, dW, g0, g1
         return dx, dh, dW, None, None
@@ -2041,11 +1991,7 @@ class _DenseLNAct(Function):
         N, K = W.shape
         assert K == K1 + K2
         pre = torch.empty(M, N, device=a.device)
-        w1, ld1 = _aligned_block(W, K1, M)
-        sgemm(a, K1, 1, w1, ld1, 1, pre, N, b, M, N, K1)
-        if c is not None:
-            sgemm(c, K2, 1, W, K, 1, pre, N, None, M, N, K2, accumulate=True, b_off=K1)
-        ctx.w1 = (w1, ld1)
+        ctx.w1 = _dense2_fwd(a, c, W, b, pre)
         y = torch.empty_like(pre)
         mean = torch.empty(M, device=a.device); rstd = torch.empty(M, device=a.device)
         check(lib().genrl_ln_act_fwd(_p(pre), N, _p(gamma), _p(beta), _p(y), N, _p(mean), _p(rstd), M, N, eps, 1,
@@ -2062,7 +2008,7 @@ class _DenseLNAct(Function):
         a, c, W, gamma, beta, pre, mean, rstd = ctx.saved_tensors
         M, K1 = a.shape
         K2 = c.shape[1] if ctx.has2 else 0
-        N, K = W.shape
+        N = W.shape[0]
         dev = dy.device
         dy2 = dy.reshape(M, N).contiguous()
         dpre = torch.empty_like(pre)          # gradient w.r.t. the pre-LayerNorm projection
@@ -2070,28 +2016,11 @@ class _DenseLNAct(Function):
         g0, g1, g2, ws, acc_p, direct = _ln_param_targets(M, N, gamma, beta, ctx.bias, dev, need=need_p)
         check(lib().genrl_ln_act_bwd(_p(dy2), N, _p(pre), N, _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dpre), N,
                                      _p(g0), _p(g1), _p(g2), _p(ws), M, N, 1, acc_p, _stream()), 'ln_act_bwd')
-        d1 = d2 = dW = None
-        if ctx.needs_input_grad[0]:
-            d1 = torch.empty(M, K1, device=dev)
-            sgemm(dpre, N, 1, ctx.w1[0], 1, ctx.w1[1], d1, K1, None, M, K1, N)
-            d1 = d1.reshape(ctx.shapes[0])
-        if ctx.has2 and ctx.needs_input_grad[1]:
-            d2 = torch.empty(M, K2, device=dev)
-            sgemm(dpre, N, 1, W, 1, K, d2, K2, None, M, K2, N, b_off=K1)
-            d2 = d2.reshape(ctx.shapes[1])
-        if ctx.needs_input_grad[2]:
-            tgt, acc, dW = _wgrad_target(W)
-            def wg():
-                sgemm(dpre, 1, N, a, 1, K1, tgt, K, None, N, K1, M, accumulate=acc)
-                if ctx.has2:
-                    sgemm(dpre, 1, N, c, 1, K2, tgt, K, None, N, K2, M, accumulate=acc, c_off=K1)
-            if acc:
-                wgrad_stream.run(wg, dpre, a, c)
-            else:
-                wg()
+        d1, d2 = _dense2_dgrad(dpre, W, ctx.w1, K1, K2, ctx.needs_input_grad[0], ctx.has2 and ctx.needs_input_grad[1])
+        dW = _dense2_wgrad(dpre, a, c if ctx.has2 else None, W) if ctx.needs_input_grad[2] else None
         if need_p and not direct:
-            return d1, d2, dW, (g2 if ctx.has_bias else None), g0, g1, None
-        return d1, d2, dW, None, None, None, None
+            return _as(d1, ctx.shapes[0]), _as(d2, ctx.shapes[1]), dW, (g2 if ctx.has_bias else None), g0, g1, None
+        return _as(d1, ctx.shapes[0]), _as(d2, ctx.shapes[1]), dW, None, None, None, None
 
 
 def dense_ln_act(x1, x2, W, b, gamma, beta, eps=1e-5):
@@ -2529,11 +2458,7 @@ class _DenseAct(Function):
         N, K = W.shape
         assert K == K1 + K2 and N % 4 == 0
         pre = torch.empty(M, N, device=a.device)
-        w1, ld1 = _aligned_block(W, K1, M)
-        sgemm(a, K1, 1, w1, ld1, 1, pre, N, None, M, N, K1)
-        if c is not None:
-            sgemm(c, K2, 1, W, K, 1, pre, N, None, M, N, K2, accumulate=True, b_off=K1)
-        ctx.w1 = (w1, ld1)
+        ctx.w1 = _dense2_fwd(a, c, W, None, pre)
         y = torch.empty_like(pre)
         silu_fwd_raw(pre, y, M, N)
         ctx.save_for_backward(a, c if c is not None else a.new_empty(0), W, pre)
@@ -2546,30 +2471,12 @@ class _DenseAct(Function):
         a, c, W, pre = ctx.saved_tensors
         M, K1 = a.shape
         K2 = c.shape[1] if ctx.has2 else 0
-        N, K = W.shape
-        dev = dy.device
+        N = W.shape[0]
         dpre = torch.empty_like(pre)
         silu_bwd_raw(_f32(dy).reshape(M, N).contiguous(), pre, dpre, M, N)
-        d1 = d2 = dW = None
-        if ctx.needs_input_grad[0]:
-            d1 = torch.empty(M, K1, device=dev)
-            sgemm(dpre, N, 1, ctx.w1[0], 1, ctx.w1[1], d1, K1, None, M, K1, N)
-            d1 = d1.reshape(ctx.shapes[0])
-        if ctx.has2 and ctx.needs_input_grad[1]:
-            d2 = torch.empty(M, K2, device=dev)
-            sgemm(dpre, N, 1, W, 1, K, d2, K2, None, M, K2, N, b_off=K1)
-            d2 = d2.reshape(ctx.shapes[1])
-        if ctx.needs_input_grad[2]:
-            tgt, acc, dW = _wgrad_target(W)
-            def wg():
-                sgemm(dpre, 1, N, a, 1, K1, tgt, K, None, N, K1, M, accumulate=acc)
-                if ctx.has2:
-                    sgemm(dpre, 1, N, c, 1, K2, tgt, K, None, N, K2, M, accumulate=acc, c_off=K1)
-            if acc:
-                wgrad_stream.run(wg, dpre, a, c)
-            else:
-                wg()
-        return d1, d2, dW
+        d1, d2 = _dense2_dgrad(dpre, W, ctx.w1, K1, K2, ctx.needs_input_grad[0], ctx.has2 and ctx.needs_input_grad[1])
+        dW = _dense2_wgrad(dpre, a, c if ctx.has2 else None, W) if ctx.needs_input_grad[2] else None
+        return _as(d1, ctx.shapes[0]), _as(d2, ctx.shapes[1]), dW
 
 
 def dense_act(x1, x2, W):

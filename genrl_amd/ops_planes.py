@@ -106,7 +106,7 @@ class ActorTapePlanes(ops.ActorTape):
                 sp_ = getattr(self, 'state_planes', None)
                 tn = tn and sp_ is not None and self.inputs[0].shape[-1] % 4 == 0
             # the fp32 copy of the pre-activation gradient has one reader, the fp32-operand weight-gradient kernel: with that product on
-            # planes the LayerNorm backward writes planes only (as _DenseLNActPlanes.backward), where its kernel writes planes itself
+            # planes the LayerNorm backward writes planes only (as _TrunkPlanes.backward), where its kernel writes planes itself
             planes_only = tn and 256 < U <= 4096 and U % 4 == 0
             dpre = None if planes_only else torch.empty(M, U, device=dev)
             if dpre_p is None or dpre_p.cols != U:
@@ -290,94 +290,65 @@ class _RolloutPlanes(Function):
         return ops._rollout_param_grads(tape, d_raws)
 
 
-class _DenseLNActPlanes(Function):
-    """ops._DenseLNAct (y = SiLU(LayerNorm([x1, x2] W^T + b)), agent/dreamer_utils.py:739-747) with plane operands: the forward
-    product runs on planes when the inputs come with them (P1 / P2: Planes handles + first row), the output's planes are written by
-    the LayerNorm kernel (out_p), and the backward's dgrad products use the planes its LayerNorm backward emits and the
-    transposed weight planes.  Weight gradients: fp32-operand kernels, as everywhere."""
-    @staticmethod
-    def forward(ctx, x1, x2, W, b, gamma, beta, eps, P1, r1, P2, r2, out_p):
-        a = _f32(x1).reshape(-1, x1.shape[-1]).contiguous()
-        c = _f32(x2).reshape(-1, x2.shape[-1]).contiguous() if x2 is not None else None
-        M, K1 = a.shape
-        K2 = c.shape[1] if c is not None else 0
-        N, K = W.shape
-        assert K == K1 + K2
-        pre = torch.empty(M, N, device=a.device)
-        y = torch.empty_like(pre)
-        mean = torch.empty(M, device=a.device); rstd = torch.empty(M, device=a.device)
-        on_planes = P1 is not None and (c is None or P2 is not None)
-        if on_planes and planes.gemm_ln_ok(M, N, a.device):
-            # product + LayerNorm + SiLU in ONE launch (row statistics exchanged inside one XCD's L2: genrl_gemm_h2_ln)
-            if c is None:
-                planes.gemm_ln(P1, planes.weight(W), pre, b, M, N, gamma, beta, eps, out_p, 0, y=y, mean=mean, rstd=rstd, a_row0=r1)
-            else:
-                planes.gemm_ln(P1, planes.weight(W, c0=0, c1=K1), pre, b, M, N, gamma, beta, eps, out_p, 0, y=y, mean=mean, rstd=rstd,
-                               a_row0=r1, A1=P2, B1=planes.weight(W, c0=K1), a1_row0=r2)
-        else:
-            if on_planes:
-                if c is None:
-                    planes.gemm(P1, planes.weight(W), pre, N, b, M, N, a_row0=r1)
-                else:
-                    planes.gemm(P1, planes.weight(W, c0=0, c1=K1), pre, N, b, M, N, a_row0=r1, A1=P2, B1=planes.weight(W, c0=K1), a1_row0=r2)
-            else:
-                w1, ld1 = ops._aligned_block(W, K1, M)
-                sgemm(a, K1, 1, w1, ld1, 1, pre, N, b, M, N, K1)
-                if c is not None:
-                    sgemm(c, K2, 1, W, K, 1, pre, N, None, M, N, K2, accumulate=True, b_off=K1)
-            _ln_fwd(_p(pre), gamma, beta, _p(y), _p(mean), _p(rstd), M, N, eps, out_p, 0)
-        ctx.save_for_backward(a, c if c is not None else a.new_empty(0), W, gamma, beta, pre, mean, rstd)
-        ctx.has2 = c is not None
-        ctx.bias = b
-        # the inputs' planes serve the weight gradient again (genrl_gemm_h2_tn): kept with the node
-        # (only when that product will really take them: otherwise the fp16 copies would live from forward to backward for nothing)
-        keep = (P1 is not None and (c is None or P2 is not None) and ctx.needs_input_grad[2] and planes.tn_ok(M, N, K1, K)
-                and (c is None or K2 % 4 == 0) and r1 % 4 == 0 and r2 % 4 == 0)
-        ctx.in_planes = ((P1, r1), (P2, r2)) if keep else None
-        ctx.shapes = (x1.shape, x2.shape if x2 is not None else None)
-        return y.reshape(*x1.shape[:-1], N)
+# ---- the dense layer on [x1, x2] with plane operands: its three products, defined once for the nodes below (on fp32 operands: ops._dense2_*)
 
-    @staticmethod
-    def backward(ctx, dy):
-        a, c, W, gamma, beta, pre, mean, rstd = ctx.saved_tensors
-        M, K1 = a.shape
-        K2 = c.shape[1] if ctx.has2 else 0
-        N, K = W.shape
-        dev = dy.device
-        b = ctx.bias
-        dy2 = dy.reshape(M, N).contiguous()
-        ip = ctx.in_planes
-        use_tn = ip is not None and planes.tn_ok(M, N, K1, K) and (not ctx.has2 or K2 % 4 == 0)
-        # the fp32 copy of the pre-activation gradient has one reader, the fp32-operand weight-gradient kernel: with that product
-        # on planes (genrl_gemm_h2_tn) the LayerNorm backward writes planes only (a quarter of its traffic less)
-        planes_only = 256 < N <= 4096 and N % 4 == 0          # (the LayerNorm kernels that write planes themselves)
-        dpre = torch.empty_like(pre) if ((ctx.needs_input_grad[2] and not use_tn) or not planes_only) else None
-        dpre_p = planes.Planes(M, N, dev)
-        need_p = ctx.needs_input_grad[2] or ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
-        g0, g1, g2, ws, acc_p, direct = _ln_param_targets(M, N, gamma, beta, b, dev, need=need_p)
-        _ln_bwd(_p(dy2), _p(pre), gamma, beta, _p(mean), _p(rstd), _p(dpre) if dpre is not None else None, M, N, dpre_p, 0, g0, g1, g2, ws, acc_p)
-        d1 = d2 = dW = None
-        if ctx.needs_input_grad[0]:
-            d1 = torch.empty(M, K1, device=dev)
-            planes.gemm(dpre_p, planes.weight(W, True, 0, K1), d1, K1, None, M, K1)
-            d1 = d1.reshape(ctx.shapes[0])
-        if ctx.has2 and ctx.needs_input_grad[1]:
-            d2 = torch.empty(M, K2, device=dev)
-            planes.gemm(dpre_p, planes.weight(W, True, K1), d2, K2, None, M, K2)
-            d2 = d2.reshape(ctx.shapes[1])
-        if ctx.needs_input_grad[2]:
-            tgt, acc, dW = _wgrad_target(W)
-            if use_tn:
-                planes.gemm_tn(dpre_p, ip[0][0], tgt, K, N, K1, M, accumulate=acc, b_row0=ip[0][1])
-                if ctx.has2:
-                    planes.gemm_tn(dpre_p, ip[1][0], tgt, K, N, K2, M, accumulate=acc, b_row0=ip[1][1], c_off=K1)
-            else:
-                sgemm(dpre, 1, N, a, 1, K1, tgt, K, None, N, K1, M, accumulate=acc)
-                if ctx.has2:
-                    sgemm(dpre, 1, N, c, 1, K2, tgt, K, None, N, K2, M, accumulate=acc, c_off=K1)
-        if need_p and not direct:
-            return d1, d2, dW, (g2 if b is not None else None), g0, g1, None, None, None, None, None, None
-        return d1, d2, dW, None, None, None, None, None, None, None, None, None
+def _dense_fwd(M, in1, in2, W, b, pre, need_w, ln=None):
+    """pre (M, N) = [x1, x2] W^T (+ b) and, with ln = (gamma, beta, eps, out_p, y, mean, rstd), y / out_p = SiLU(LayerNorm(pre)) (y None: planes
+    only).  in1 / in2: (fp32 rows, Planes | None, first row) of the inputs; fp32 rows of in2 None: one input.  The product runs on planes when
+    every input comes with them -- with the LayerNorm and the SiLU in ONE launch where planes.gemm_ln_ok holds (row statistics exchanged inside one
+    XCD's L2: genrl_gemm_h2_ln) -- else on the fp32 rows (ops._dense2_fwd).
+    -> the inputs' ((P1, r1), (P2, r2)) for the node to keep, where the weight gradient (need_w: somebody wants it) will really take them
+    (genrl_gemm_h2_tn); else None: the fp16 copies would live from forward to backward for nothing"""
+    (a, Pa, ra), (c, Pb, rb) = in1, in2
+    N, K = W.shape
+    two = c is not None
+    K1 = a.shape[1] if two else K
+    on_planes = Pa is not None and (not two or Pb is not None)
+    fused = on_planes and ln is not None and planes.gemm_ln_ok(M, N, pre.device)
+    if on_planes:
+        # (two inputs: ONE launch with two operand segments, the column blocks of W)
+        w1 = planes.weight(W, c0=0, c1=K1)
+        seg = dict(a_row0=ra, A1=Pb, B1=planes.weight(W, c0=K1), a1_row0=rb) if two else dict(a_row0=ra)
+        if fused:
+            gamma, beta, eps, out_p, y, mean, rstd = ln
+            planes.gemm_ln(Pa, w1, pre, b, M, N, gamma, beta, eps, out_p, 0, y=y, mean=mean, rstd=rstd, **seg)
+        else:
+            planes.gemm(Pa, w1, pre, N, b, M, N, **seg)
+    else:
+        ops._dense2_fwd(a, c, W, b, pre)
+    if ln is not None and not fused:
+        gamma, beta, eps, out_p, y, mean, rstd = ln
+        _ln_fwd(_p(pre), gamma, beta, _p(y), _p(mean), _p(rstd), M, N, eps, out_p, 0)
+    keep = on_planes and need_w and planes.tn_ok(M, N, K1, K) and (not two or (K - K1) % 4 == 0) and ra % 4 == 0 and rb % 4 == 0
+    return ((Pa, ra), (Pb, rb)) if keep else None
+
+
+def _dense_dgrad(dpre_p, W, K1, need1, need2):
+    """-> (d1, d2) = dpre W[:, :K1] (M, K1), dpre W[:, K1:] (M, K - K1) from the planes of dpre and the transposed weight planes; None where
+    not needed"""
+    M, K2 = dpre_p.rows, W.shape[1] - K1
+    d1 = d2 = None
+    if need1:
+        d1 = torch.empty(M, K1, device=W.device)
+        planes.gemm(dpre_p, planes.weight(W, True, 0, K1), d1, K1, None, M, K1)
+    if need2:
+        d2 = torch.empty(M, K2, device=W.device)
+        planes.gemm(dpre_p, planes.weight(W, True, K1), d2, K2, None, M, K2)
+    return d1, d2
+
+
+def _dense_wgrad(dpre_p, dpre, ip, a, c, W):
+    """dW = dpre^T [x1, x2], written or added where _wgrad_target says: genrl_gemm_h2_tn on the planes of dpre and the input planes the node
+    kept (ip: what _dense_fwd returned), else -- ip None -- the fp32-operand kernels on dpre and the inputs' fp32 rows (ops._dense2_wgrad).
+    c None: one input.  -> what the node returns to autograd for W"""
+    if ip is None:
+        return ops._dense2_wgrad(dpre, a, c, W)
+    (N, K), M, K1 = W.shape, dpre_p.rows, ip[0][0].cols
+    tgt, acc, dW = _wgrad_target(W)
+    planes.gemm_tn(dpre_p, ip[0][0], tgt, K, N, K1, M, accumulate=acc, b_row0=ip[0][1])
+    if c is not None:
+        planes.gemm_tn(dpre_p, ip[1][0], tgt, K, N, K - K1, M, accumulate=acc, b_row0=ip[1][1], c_off=K1)
+    return dW
 
 
 class _LinearPlanes(Function):
@@ -451,9 +422,10 @@ def min_rows():
     return int(os.environ.get('GENRL_PLANES_MIN_ROWS', MIN_ROWS_PLANES))
 
 
-def _ln_input_handles(x1, x2, planes_):
-    """(P1, r1), (P2, r2) of dense_ln_act's inputs: the caller's ((P1, row0), (P2, row0) | None), else the inputs' own `_planes` attribute
-    (a previous layer's output); dropped where they do not cover the rows -- and both where the second input comes without"""
+def _input_handles(x1, x2, planes_, both_or_none):
+    """(P1, r1), (P2, r2) of dense_ln_act's / dense_act's inputs: the caller's ((P1, row0), (P2, row0) | None), else the inputs' own `_planes`
+    attribute (a previous layer's output); dropped where they do not cover the rows.  A second input that comes without: both_or_none (the
+    LayerNorm layers, whose product then runs on the fp32 rows) drops the first input's too; the norm-free layer keeps them and splits the second"""
     M = x1.numel() // x1.shape[-1]
     if planes_ is None:
         h1 = getattr(x1, '_planes', None)
@@ -462,28 +434,28 @@ def _ln_input_handles(x1, x2, planes_):
         h1, h2 = planes_[0], (planes_[1] if len(planes_) > 1 else None)
     if h1 is not None and (h1[0].cols != x1.shape[-1] or h1[1] + M > h1[0].rows):
         h1 = None
-    if x2 is not None and (h2 is None or h2[0].cols != x2.shape[-1] or h2[1] + M > h2[0].rows):
-        h1 = h2 = None
+    if x2 is not None and h2 is not None and (h2[0].cols != x2.shape[-1] or h2[1] + M > h2[0].rows):
+        h2 = None
+    if both_or_none and x2 is not None and h2 is None:
+        h1 = None
     return (h1 if h1 is not None else (None, 0)), (h2 if h2 is not None else (None, 0))
 
 
 def dense_ln_act(x1, x2, W, b, gamma, beta, eps=1e-5, planes=None):
-    """-> y with y._planes = (planes of y, 0) for the next layer.  planes = ((P1, row0), (P2, row0) | None) of the inputs when the
-    caller has them (rollout states); otherwise the inputs' own `_planes` attribute (a previous layer's output) is used."""
-    M = x1.numel() // x1.shape[-1]
-    N = W.shape[0]
-    (P1, r1), (P2, r2) = _ln_input_handles(x1, x2, planes)
-    out_p = pl.Planes(M, N, x1.device)
-    y = _DenseLNActPlanes.apply(x1, x2, W, b, gamma, beta, float(eps), P1, r1, P2, r2, out_p)
-    y._planes = (out_p, 0)
-    return y
+    """y = SiLU(LayerNorm([x1, x2] W^T + b)) (ops.dense_ln_act, agent/dreamer_utils.py:739-747) on plane operands: a trunk of one layer.
+    -> y with y._planes = (planes of y, 0) for the next layer.  planes = ((P1, row0), (P2, row0) | None) of the inputs when the caller has them
+    (rollout states); otherwise the inputs' own `_planes` attribute (a previous layer's output) is used."""
+    return dense_ln_trunk(x1, x2, [(W, b, gamma, beta, eps)], planes=planes)
 
 
 class _TrunkPlanes(Function):
-    """A chain of _DenseLNActPlanes layers (an MLP trunk: agent/dreamer_utils.py:739-747) as ONE autograd node, the way ActorTapePlanes
-    treats the policy: the same launches in the same order, forward and backward, as the per-layer chain -- bit-identical outputs and
-    gradients, the same accumulation order into the flat gradient buffers -- but a hidden layer's output is consumed inside the node, as
-    planes, so its fp32 copy is written only where somebody reads it: the NEXT layer's weight gradient while it stays on the fp32-operand
+    """A chain of layers y = SiLU(LayerNorm([x1, x2] W^T + b)) (ops._DenseLNAct; an MLP trunk: agent/dreamer_utils.py:739-747) with plane
+    operands as ONE autograd node, the way ActorTapePlanes treats the policy.  Per layer: the forward product runs on planes when the inputs
+    come with them, the output's planes are written by the LayerNorm kernel, the backward's dgrad products use the planes its LayerNorm
+    backward emits and the transposed weight planes, the weight gradient the kept input planes or the fp32-operand kernels (_dense_fwd /
+    _dense_dgrad / _dense_wgrad).  The same launches in the same order, forward and backward, as a chain of one-layer nodes -- bit-identical
+    outputs and gradients, the same accumulation order into the flat gradient buffers -- but a hidden layer's output is consumed inside the
+    node, as planes, so its fp32 copy is written only where somebody reads it: the NEXT layer's weight gradient while it stays on the fp32-operand
     kernel (below planes.tn_min_rows() rows), or a LayerNorm kernel that cannot write planes without it.  No tensor with undefined contents
     leaves the node: the caller gets the last layer's fp32 output alone.  params: (W, b, gamma, beta) per layer; out_ps: the output planes
     per layer; P1 / P2 (+ first rows): the planes of layer 0's inputs, or None."""
@@ -502,38 +474,16 @@ class _TrunkPlanes(Function):
             N, K = W.shape
             if l == 0:
                 assert K == K1 + K2
-                Pa, ra, Pb, rb, k1, k2 = P1, r1, P2, r2, K1, K2
+                in1, in2 = (a, P1, r1), (c, P2, r2)
             else:
-                Pa, ra, Pb, rb, k1, k2 = out_ps[l - 1], 0, None, 0, K, 0
-            two = l == 0 and c is not None
+                in1, in2 = (None, out_ps[l - 1], 0), (None, None, 0)
             # the fp32 copy of this layer's output: the node's result (last layer), else see the class comment
             keep_y = l == L - 1 or not (256 < N <= 4096 and N % 4 == 0
                                         and (not needs_w[l + 1] or planes.tn_ok(M, params[4 * (l + 1)].shape[0], N, N)))
             pre = torch.empty(M, N, device=dev)
             y = torch.empty(M, N, device=dev) if keep_y else None
             mean = torch.empty(M, device=dev); rstd = torch.empty(M, device=dev)
-            on_planes = Pa is not None and (not two or Pb is not None)
-            if on_planes and planes.gemm_ln_ok(M, N, dev):
-                if not two:
-                    planes.gemm_ln(Pa, planes.weight(W), pre, b, M, N, gamma, beta, eps[l], out_ps[l], 0, y=y, mean=mean, rstd=rstd, a_row0=ra)
-                else:
-                    planes.gemm_ln(Pa, planes.weight(W, c0=0, c1=k1), pre, b, M, N, gamma, beta, eps[l], out_ps[l], 0, y=y, mean=mean, rstd=rstd,
-                                   a_row0=ra, A1=Pb, B1=planes.weight(W, c0=k1), a1_row0=rb)
-            else:
-                if on_planes:
-                    if not two:
-                        planes.gemm(Pa, planes.weight(W), pre, N, b, M, N, a_row0=ra)
-                    else:
-                        planes.gemm(Pa, planes.weight(W, c0=0, c1=k1), pre, N, b, M, N, a_row0=ra, A1=Pb, B1=planes.weight(W, c0=k1), a1_row0=rb)
-                else:                    # (layer 0 alone: an input that came without planes)
-                    w1, ld1 = ops._aligned_block(W, k1, M)
-                    sgemm(a, k1, 1, w1, ld1, 1, pre, N, b, M, N, k1)
-                    if two:
-                        sgemm(c, k2, 1, W, K, 1, pre, N, None, M, N, k2, accumulate=True, b_off=k1)
-                _ln_fwd(_p(pre), gamma, beta, _p(y), _p(mean), _p(rstd), M, N, eps[l], out_ps[l], 0)
-            # the inputs' planes serve the weight gradient again (genrl_gemm_h2_tn): kept only when that product will really take them
-            keep = (on_planes and needs_w[l] and planes.tn_ok(M, N, k1, K) and (not two or k2 % 4 == 0) and ra % 4 == 0 and rb % 4 == 0)
-            in_planes.append(((Pa, ra), (Pb, rb)) if keep else None)
+            in_planes.append(_dense_fwd(M, in1, in2, W, b, pre, needs_w[l], (gamma, beta, eps[l], out_ps[l], y, mean, rstd)))
             pres.append(pre); means.append(mean); rstds.append(rstd); ys.append(y)
         ctx.save_for_backward(a, c if c is not None else a.new_empty(0), *params[0::4], *params[2::4], *params[3::4])
         ctx.biases = list(params[1::4])
@@ -571,32 +521,18 @@ class _TrunkPlanes(Function):
             need_p = need_w or need_b or need_g
             g0, g1, g2, ws, acc_p, direct = _ln_param_targets(M, N, gamma, beta, b, dev, need=need_p)
             _ln_bwd(_p(dyl), _p(ctx.pres[l]), gamma, beta, _p(ctx.means[l]), _p(ctx.rstds[l]), _p(dpre), M, N, dpre_p, 0, g0, g1, g2, ws, acc_p)
-            d1 = d2 = dW = None
-            if need_x1:
-                d1 = torch.empty(M, K1, device=dev)
-                planes.gemm(dpre_p, planes.weight(W, True, 0, K1), d1, K1, None, M, K1)
-            if has2 and ng[1]:
-                d2 = torch.empty(M, K2, device=dev)
-                planes.gemm(dpre_p, planes.weight(W, True, K1), d2, K2, None, M, K2)
+            d1, d2 = _dense_dgrad(dpre_p, W, K1, need_x1, has2 and ng[1])
+            dW = None
             if need_w:
-                tgt, acc, dW = _wgrad_target(W)
-                if use_tn:
-                    planes.gemm_tn(dpre_p, ip[0][0], tgt, K, N, K1, M, accumulate=acc, b_row0=ip[0][1])
-                    if has2:
-                        planes.gemm_tn(dpre_p, ip[1][0], tgt, K, N, K2, M, accumulate=acc, b_row0=ip[1][1], c_off=K1)
-                else:
-                    xin = a if l == 0 else ctx.hidden_y[l - 1]
-                    assert xin is not None, 'the fp32 input of a weight gradient on the fp32-operand kernel was not kept'
-                    sgemm(dpre, 1, N, xin, 1, K1, tgt, K, None, N, K1, M, accumulate=acc)
-                    if has2:
-                        sgemm(dpre, 1, N, c, 1, K2, tgt, K, None, N, K2, M, accumulate=acc, c_off=K1)
+                xin = a if l == 0 else ctx.hidden_y[l - 1]
+                assert use_tn or xin is not None, 'the fp32 input of a weight gradient on the fp32-operand kernel was not kept'
+                dW = _dense_wgrad(dpre_p, dpre, ip if use_tn else None, xin, c if has2 else None, W)
             if need_p and not direct:
                 out[8 + 4 * l:12 + 4 * l] = [dW, (g2 if b is not None else None), g0, g1]
             else:
                 out[8 + 4 * l] = dW
             if l == 0:
-                out[0] = d1.reshape(ctx.shapes[0]) if d1 is not None else None
-                out[1] = d2.reshape(ctx.shapes[1]) if d2 is not None else None
+                out[0], out[1] = ops._as(d1, ctx.shapes[0]), ops._as(d2, ctx.shapes[1])
             dyl = d1
             if dyl is None:          # (nothing upstream wants a gradient: the per-layer chain stops here too)
                 break
@@ -608,7 +544,7 @@ def dense_ln_trunk(x1, x2, layers, planes=None):
     -> the last layer's output, with its `_planes` for the head's product; the same values and gradients as dense_ln_act layer by layer
     (see _TrunkPlanes); `planes` as dense_ln_act's"""
     M = x1.numel() // x1.shape[-1]
-    (P1, r1), (P2, r2) = _ln_input_handles(x1, x2, planes)
+    (P1, r1), (P2, r2) = _input_handles(x1, x2, planes, True)
     out_ps = [pl.Planes(M, l[0].shape[0], x1.device) for l in layers]
     flat = [q for l in layers for q in l[:4]]
     y = _TrunkPlanes.apply(x1, x2, P1, r1, P2, r2, [float(l[4]) for l in layers], out_ps, *flat)
@@ -635,16 +571,11 @@ class _DenseActPlanes(Function):
         if c is not None and P2 is None:
             P2, r2 = planes.split(c.detach()), 0
         pre = torch.empty(M, N, device=a.device)
-        if c is None:
-            planes.gemm(P1, planes.weight(W), pre, N, None, M, N, a_row0=r1)
-        else:
-            planes.gemm(P1, planes.weight(W, c0=0, c1=K1), pre, N, None, M, N, a_row0=r1, A1=P2, B1=planes.weight(W, c0=K1), a1_row0=r2)
+        ctx.in_planes = _dense_fwd(M, (a, P1, r1), (c, P2, r2), W, None, pre, ctx.needs_input_grad[2])
         y = torch.empty_like(pre)
         ops.silu_fwd_raw(pre, y, M, N, out_p)
         ctx.save_for_backward(a, c if c is not None else a.new_empty(0), W, pre)
         ctx.has2 = c is not None
-        keep = (ctx.needs_input_grad[2] and planes.tn_ok(M, N, K1, K) and (c is None or K2 % 4 == 0) and r1 % 4 == 0 and r2 % 4 == 0)
-        ctx.in_planes = ((P1, r1), (P2, r2)) if keep else None
         ctx.shapes = (x1.shape, x2.shape if x2 is not None else None)
         return y.reshape(*x1.shape[:-1], N)
 
@@ -652,55 +583,19 @@ class _DenseActPlanes(Function):
     def backward(ctx, dy):
         a, c, W, pre = ctx.saved_tensors
         M, K1 = a.shape
-        K2 = c.shape[1] if ctx.has2 else 0
-        N, K = W.shape
-        dev = dy.device
-        ip = ctx.in_planes
+        N = W.shape[0]
         dpre = torch.empty_like(pre)
-        dpre_p = planes.Planes(M, N, dev)
+        dpre_p = planes.Planes(M, N, dy.device)
         ops.silu_bwd_raw(_f32(dy).reshape(M, N).contiguous(), pre, dpre, M, N, dpre_p)
-        d1 = d2 = dW = None
-        if ctx.needs_input_grad[0]:
-            d1 = torch.empty(M, K1, device=dev)
-            planes.gemm(dpre_p, planes.weight(W, True, 0, K1), d1, K1, None, M, K1)
-            d1 = d1.reshape(ctx.shapes[0])
-        if ctx.has2 and ctx.needs_input_grad[1]:
-            d2 = torch.empty(M, K2, device=dev)
-            planes.gemm(dpre_p, planes.weight(W, True, K1), d2, K2, None, M, K2)
-            d2 = d2.reshape(ctx.shapes[1])
-        if ctx.needs_input_grad[2]:
-            tgt, acc, dW = _wgrad_target(W)
-            if ip is not None:
-                planes.gemm_tn(dpre_p, ip[0][0], tgt, K, N, K1, M, accumulate=acc, b_row0=ip[0][1])
-                if ctx.has2:
-                    planes.gemm_tn(dpre_p, ip[1][0], tgt, K, N, K2, M, accumulate=acc, b_row0=ip[1][1], c_off=K1)
-            else:
-                sgemm(dpre, 1, N, a, 1, K1, tgt, K, None, N, K1, M, accumulate=acc)
-                if ctx.has2:
-                    sgemm(dpre, 1, N, c, 1, K2, tgt, K, None, N, K2, M, accumulate=acc, c_off=K1)
-        return d1, d2, dW, None, None, None, None, None
-
-
-def _input_planes(x1, x2, planes_):
-    """the (Planes, first row) handles dense_ln_act / dense_act take for their inputs: the caller's, or the inputs' own `_planes`
-    attribute (a previous layer's output); dropped where they do not cover the rows"""
-    M = x1.numel() // x1.shape[-1]
-    if planes_ is None:
-        h1 = getattr(x1, '_planes', None)
-        h2 = getattr(x2, '_planes', None) if x2 is not None else None
-    else:
-        h1, h2 = planes_[0], (planes_[1] if len(planes_) > 1 else None)
-    if h1 is not None and (h1[0].cols != x1.shape[-1] or h1[1] + M > h1[0].rows):
-        h1 = None
-    if x2 is not None and h2 is not None and (h2[0].cols != x2.shape[-1] or h2[1] + M > h2[0].rows):
-        h2 = None
-    return (h1 if h1 is not None else (None, 0)), (h2 if h2 is not None else (None, 0))
+        d1, d2 = _dense_dgrad(dpre_p, W, K1, ctx.needs_input_grad[0], ctx.has2 and ctx.needs_input_grad[1])
+        dW = _dense_wgrad(dpre_p, dpre, ctx.in_planes, a, c if ctx.has2 else None, W) if ctx.needs_input_grad[2] else None
+        return ops._as(d1, ctx.shapes[0]), ops._as(d2, ctx.shapes[1]), dW, None, None, None, None, None
 
 
 def dense_act(x1, x2, W, planes=None):
     """-> y = SiLU([x1, x2] W^T) with y._planes = (planes of y, 0) for the next layer; `planes` as dense_ln_act's"""
     M = x1.numel() // x1.shape[-1]
-    (P1, r1), (P2, r2) = _input_planes(x1, x2, planes)
+    (P1, r1), (P2, r2) = _input_handles(x1, x2, planes, False)
     out_p = pl.Planes(M, W.shape[0], x1.device)
     y = _DenseActPlanes.apply(x1, x2, W, P1, r1, P2, r2, out_p)
     y._planes = (out_p, 0)

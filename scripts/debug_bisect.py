@@ -5,7 +5,7 @@ import test_gpu_iteration as T
 from genrl_amd import config, ops
 from oracle import genrl_oracle as O
 
-orig = {k: getattr(ops, k) for k in ['maxcos', 'lambda_return', 'twohot_mean', 'actor_sample', 'gru_step', 'linear2', 'onehot_sample', 'ln_act', 'linear']}
+orig = {k: getattr(ops, k) for k in ['maxcos', 'lambda_return', 'twohot_mean', 'actor_sample', 'gru_step', 'onehot_sample', 'ln_act', 'linear']}
 def t_maxcos(u, v, urow=None):
     u2 = u.reshape(-1, u.shape[-1])[urow] if urow is not None else u
     return O.max_cosine_similarity(u2.detach(), v)
@@ -22,13 +22,11 @@ def t_gru(x, h, W, g, b):
     r, c, u = torch.chunk(parts, 3, -1)
     r = torch.sigmoid(r); c = torch.tanh(r * c); u = torch.sigmoid(u - 1.0)
     return u * c + (1 - u) * h
-def t_lin2(x1, x2, W, b=None):
-    return F.linear(torch.cat([x1, x2], -1), W, b)
 def t_onehot(l, q): return O.onehot_sample(l, q)
 def t_ln(x, g, b, eps=1e-5, act=True):
     y = F.layer_norm(x, (x.shape[-1],), g, b, eps); return F.silu(y) if act else y
 def t_linear(x, W, b=None): return F.linear(x, W, b)
-rep = dict(maxcos=t_maxcos, lambda_return=t_lambda, twohot_mean=t_thmean, actor_sample=t_actor, gru_step=t_gru, linear2=t_lin2, onehot_sample=t_onehot, ln_act=t_ln, linear=t_linear)
+rep = dict(maxcos=t_maxcos, lambda_return=t_lambda, twohot_mean=t_thmean, actor_sample=t_actor, gru_step=t_gru, onehot_sample=t_onehot, ln_act=t_ln, linear=t_linear)
 tiny_o = dict(deter=32, hidden=32, units=32, cnn_depth=4)
 for name in [None] + list(rep):
     for k, v in orig.items(): setattr(ops, k, v)

@@ -271,10 +271,27 @@ def _trunk_run(one_node, two_inputs, with_planes, frozen):
     return y.detach(), yp, hidden, grads
 
 
+@pytest.fixture(scope='module')
+def trunk_book():
+    """tests/golden/lean_imag_trunk.json: the digests of the PER-LAYER chain's output, planes and gradients on the revision where that chain
+    and the one-node trunk were two separate implementations (they share their products since: the recorded values keep the comparison
+    below anchored to an independent one)"""
+    from test_gpu_dense_nodes import Book
+    b = Book('lean_imag_trunk.json')
+    yield b
+    b.save()
+
+
+def _check_parent_trunk(book, key, one_node, chain):
+    for y, p, g in (one_node, chain):             # (recording keeps the last: the per-layer chain's)
+        book.check(key, {'y': digest(y), 'planes.t': digest(p.t), 'planes.inv': digest(p.inv),
+                         **{n: (digest(t) if t is not None else None) for n, t in g.items()}})
+
+
 @pytest.mark.parametrize('frozen', [False, True])
 @pytest.mark.parametrize('with_planes', [False, True])
 @pytest.mark.parametrize('two_inputs', [False, True])
-def test_trunk_node_is_the_per_layer_chain_without_fp32_hidden_activations(two_inputs, with_planes, frozen):
+def test_trunk_node_is_the_per_layer_chain_without_fp32_hidden_activations(trunk_book, two_inputs, with_planes, frozen):
     """(the suite runs with GENRL_TN_MIN_ROWS=64: at 128 rows every weight gradient takes the plane kernel)"""
     y1, p1, hidden, g1 = _trunk_run(True, two_inputs, with_planes, frozen)
     y0, p0, _, g0 = _trunk_run(False, two_inputs, with_planes, frozen)
@@ -286,10 +303,11 @@ def test_trunk_node_is_the_per_layer_chain_without_fp32_hidden_activations(two_i
         if g0[n] is not None:
             assert torch.equal(g1[n], g0[n]), n
     assert g1['x1'] is not None and (frozen or g1['l0.W'] is not None)
+    _check_parent_trunk(trunk_book, f'two{int(two_inputs)}.planes{int(with_planes)}.frozen{int(frozen)}', (y1, p1, g1), (y0, p0, g0))
 
 
 @pytest.mark.parametrize('frozen', [False, True])
-def test_trunk_node_below_the_plane_weight_gradient_threshold(monkeypatch, frozen):
+def test_trunk_node_below_the_plane_weight_gradient_threshold(monkeypatch, trunk_book, frozen):
     """below planes.tn_min_rows() the weight gradients read the fp32 hidden activations: the node keeps them -- unless the weights are
     frozen (a slow critic), where nobody reads them at any row count"""
     monkeypatch.setenv('GENRL_TN_MIN_ROWS', '256')
@@ -304,3 +322,4 @@ def test_trunk_node_below_the_plane_weight_gradient_threshold(monkeypatch, froze
         assert (g0[n] is None) == (g1[n] is None), n
         if g0[n] is not None:
             assert torch.equal(g1[n], g0[n]), n
+    _check_parent_trunk(trunk_book, f'tn256.frozen{int(frozen)}', (y1, p1, g1), (y0, p0, g0))
