@@ -333,8 +333,9 @@ class WorldModel(Module):  # ref :120-321
         # training rollouts: the policy's H backward passes are batched into one over all H*N rows (the tape, the fused rollout and their C
         # launch loops have the LayerNorm launches, the Normal head and the categorical sample built in: the rest goes step by step below)
         tape = state_planes = None
+        # (... and SiLU: an ELU actor or an ELU rssm leaves both, each on its own)
         if (torch.is_grad_enabled() and head_w.requires_grad and horizon > 1 and policy._norm != 'none' and rssm._norm != 'none'
-                and head.fused and lat.fused):
+                and policy._act == 'SiLU' and rssm._act == 'SiLU' and head.fused and lat.fused):
             layers = [(getattr(policy, f'dense{i}').weight, getattr(policy, f'dense{i}').bias,
                        getattr(policy, f'norm{i}')._layer.weight, getattr(policy, f'norm{i}')._layer.bias,
                        getattr(policy, f'norm{i}')._layer.eps) for i in range(policy._layers)]

@@ -6,7 +6,7 @@ pickled agents are interchangeable; every forward/backward runs in the hand-writ
 of libgenrl_hip.so (genrl_amd/ops.py).  nn.Module containers (nn.Linear, nn.Conv2d, nn.LayerNorm)
 are used only as *parameter holders*: their torch forward is never called on the hot path.
 
-What the GenRL path and the dreamer_v3 / dreamer_v2 defaults configure is implemented (norm 'layer'/'none', act SiLU, discrete or
+What the GenRL path and the dreamer_v3 / dreamer_v2 defaults configure is implemented (norm 'layer'/'none', act SiLU / ELU, discrete or
 continuous latents, GRU cell, dists mse / twohot / normal / trunc_normal / tanh_normal / onehot / symlog_mse, image_dist mse / normal_unit_std, vector
 observation keys beside or instead of one image key); other reference options raise.
 """
@@ -449,21 +449,28 @@ class ImgChLayerNorm(nn.Module):  # ref :1031-1040 (parameter holder; applied on
         return y.permute(0, 3, 1, 2)
 
 
-def _dense_ln_silu(x, lin, norm, x2=None, planes=None):
-    """Linear (+ second concatenated input) + LayerNorm + SiLU with the reference's layer objects.  planes: h2 planes of
+def _block_act(act):
+    """a block's `act:` -> the name its layers run with: 'SiLU' or 'ELU' (ops.ACTS); any other name raises NotImplementedError(name)"""
+    ops.act_code(str(act))
+    return str(act)
+
+
+def _dense_ln_silu(x, lin, norm, x2=None, planes=None, act='SiLU'):
+    """Linear (+ second concatenated input) + LayerNorm + the block's activation (act: 'SiLU' / 'ELU') with the reference's layer
+    objects.  planes: h2 planes of
     the inputs (genrl_amd/planes.py) when the caller has them.  NormLayer('none') (conf/defaults/dreamer_v2.yaml): Linear without
-    bias + SiLU (dense_act), under the same row threshold and switch.  A first input whose width is no multiple of 4 (continuous latents
+    bias + activation (dense_act), under the same row threshold and switch.  A first input whose width is no multiple of 4 (continuous latents
     with the reference's `stoch: 30`) stays on the fp32-operand kernels, whose scalar-load form takes any width and row spacing."""
     use_planes = planes_route(x.numel() // x.shape[-1], 'GENRL_PLANES_MLP', (lin.weight.shape[0], x.shape[-1]), x.is_cuda)
     if norm._layer is None:
         assert lin.bias is None, 'a norm-free layer has no bias (ref :339-346, :734)'
         if use_planes:
-            return ops_planes.dense_act(x, x2, lin.weight, planes=planes)
-        return ops.dense_act(x, x2, lin.weight)
+            return ops_planes.dense_act(x, x2, lin.weight, planes=planes, act=act)
+        return ops.dense_act(x, x2, lin.weight, act=act)
     if use_planes:          # (-0.75 ms/step at c2 with the BK-64 128x128 tile, DESIGN 4a)
         return ops_planes.dense_ln_act(x, x2, lin.weight, lin.bias, norm._layer.weight, norm._layer.bias, norm._layer.eps,
-                                   planes=planes)
-    return ops.dense_ln_act(x, x2, lin.weight, lin.bias, norm._layer.weight, norm._layer.bias, norm._layer.eps)
+                                   planes=planes, act=act)
+    return ops.dense_ln_act(x, x2, lin.weight, lin.bias, norm._layer.weight, norm._layer.bias, norm._layer.eps, act=act)
 
 
 class GRUCell(Module):  # ref :750-785
@@ -518,7 +525,7 @@ class DistLayer(Module):  # ref :787-841
 class MLP(Module):  # ref :718-747
     def __init__(self, in_shape, shape, layers, units, act='SiLU', norm='none', **out):
         super().__init__()
-        assert act == 'SiLU'
+        self._act = _block_act(act)
         self._in_shape = in_shape
         if out['dist'] == 'twohot':
             shape = 255
@@ -542,10 +549,10 @@ class MLP(Module):  # ref :718-747
             # next layer's plane product reads (ops_planes._TrunkPlanes) -- layer by layer the same launches as the loop below
             layers = [(getattr(self, f'dense{i}').weight, getattr(self, f'dense{i}').bias, getattr(self, f'norm{i}')._layer.weight,
                        getattr(self, f'norm{i}')._layer.bias, getattr(self, f'norm{i}')._layer.eps) for i in range(self._layers)]
-            x = ops_planes.dense_ln_trunk(x, x2, layers, planes=planes)
+            x = ops_planes.dense_ln_trunk(x, x2, layers, planes=planes, act=self._act)
         else:
             for index in range(self._layers):
-                x = _dense_ln_silu(x, getattr(self, f'dense{index}'), getattr(self, f'norm{index}'), x2, planes=planes)
+                x = _dense_ln_silu(x, getattr(self, f'dense{index}'), getattr(self, f'norm{index}'), x2, planes=planes, act=self._act)
                 x2 = planes = None
         out = x.reshape(list(features.shape[:-1]) + [x.shape[-1]])
         h = getattr(x, '_planes', None)        # (reshape returns a new tensor object: carry the operand planes of the rows along)
@@ -576,9 +583,9 @@ def _mlp_stack(in_dim, widths, norm, act):
     return nn.Sequential(*layers)
 
 
-def _run_mlp_stack(model, x):
+def _run_mlp_stack(model, x, act):
     for i in range(0, len(model), 3):
-        x = _dense_ln_silu(x, model[i], model[i + 1])
+        x = _dense_ln_silu(x, model[i], model[i + 1], act=act)
     return x
 
 
@@ -589,7 +596,8 @@ class Encoder(Module):  # ref :558-628
         self.shapes = shapes
         self.cnn_keys = [k for k, v in shapes.items() if re.match(cnn_keys, k) and len(v) == 3]
         self.mlp_keys = [k for k, v in shapes.items() if re.match(mlp_keys, k) and len(v) == 1]
-        assert act == 'SiLU' and norm == 'layer', 'GenRL path: SiLU + layer norm'
+        self._act = _block_act(act)
+        assert norm == 'layer', 'layer norm (both default sets)'
         assert self.cnn_keys or self.mlp_keys, 'no observation key selected'
         self._cnn_depth, self._cnn_kernels = cnn_depth, cnn_kernels
         self._mlp_layers, self._symlog_inputs = list(mlp_layers), symlog_inputs
@@ -633,7 +641,7 @@ class Encoder(Module):  # ref :558-628
             for v in xs:
                 ops.symlog_rows(v, out=x, col=col, symlog=self._symlog_inputs)
                 col += v.shape[1]
-        x = _run_mlp_stack(self._mlp_model, x)
+        x = _run_mlp_stack(self._mlp_model, x, self._act)
         return x.reshape(tuple(lead) + (x.shape[-1],))
 
     def _cnn(self, x):
@@ -647,7 +655,7 @@ class Encoder(Module):  # ref :558-628
             # (an inner layer's fp32 activation has no reader when the next layer gathers from its planes forward AND backward: decided by
             # the next layer's own predicates, ops_conv_planes.consumer_reads_planes_only -- not by position)
             nxt = True if i == last else ('conv', self._cnn_kernels[i + 1])
-            x = conv2d(x, conv.weight, conv.bias, ln=(ln.norm.weight, ln.norm.bias, ln.norm.eps), fp32_out=nxt, planes_out=i != last)
+            x = conv2d(x, conv.weight, conv.bias, ln=(ln.norm.weight, ln.norm.bias, ln.norm.eps, self._act), fp32_out=nxt, planes_out=i != last)
         n, h, w, c = x.shape
         return ops.transpose_last2(x.reshape(n, h * w, c)).reshape(n, c * h * w)    # NCHW flatten, ref :621
 
@@ -660,7 +668,8 @@ class Decoder(Module):  # ref :631-715
         self._embed_dim, self._shapes = embed_dim, shapes
         self.cnn_keys = [k for k, v in shapes.items() if re.match(cnn_keys, k) and len(v) == 3]
         self.mlp_keys = [k for k, v in shapes.items() if re.match(mlp_keys, k) and len(v) == 1]
-        assert act == 'SiLU' and norm == 'layer' and image_dist in ('mse', 'normal_unit_std')
+        self._act = _block_act(act)
+        assert norm == 'layer' and image_dist in ('mse', 'normal_unit_std')
         self._image_dist = image_dist
         assert len(self.cnn_keys) <= 1 and (self.cnn_keys or self.mlp_keys), 'one image key at most, and at least one key'
         self._cnn_depth, self._cnn_kernels = cnn_depth, cnn_kernels
@@ -693,7 +702,7 @@ class Decoder(Module):  # ref :631-715
 
     def _mlp(self, features):
         """ref :708-715: the trunk runs once and every vector key's head reads it"""
-        x = _run_mlp_stack(self._mlp_model, features.reshape(-1, features.shape[-1]))
+        x = _run_mlp_stack(self._mlp_model, features.reshape(-1, features.shape[-1]), self._act)
         x = x.reshape(tuple(features.shape[:-1]) + (x.shape[-1],))
         return {key: getattr(self, f'dense_{key}')(x) for key in self.mlp_keys}
 
@@ -711,7 +720,7 @@ class Decoder(Module):  # ref :631-715
                 # predicates say it reads planes only)
                 nconv = self._conv_model[3 * (i + 1)]
                 nxt = True if i == n - 2 else ('convT', nconv.out_channels, self._cnn_kernels[i + 1])
-                x = convT2d(x, conv.weight, conv.bias, ln=(ln.norm.weight, ln.norm.bias, ln.norm.eps), fp32_out=nxt, planes_out=i != n - 2)
+                x = convT2d(x, conv.weight, conv.bias, ln=(ln.norm.weight, ln.norm.bias, ln.norm.eps, self._act), fp32_out=nxt, planes_out=i != n - 2)
             else:
                 x = ops.convT2d_s2(x, conv.weight, conv.bias, out_nchw=True)     # frames leave in the reference's NCHW
         image_dist = NormalUnitStdDist if self._image_dist == 'normal_unit_std' else MSEDist          # ref :704
@@ -799,6 +808,9 @@ class EnsembleRSSM(Module):  # ref :302-555
         assert ensemble == 1 and cell_type == 'gru' and cell_input == 'stoch' and norm in ('layer', 'none'), \
             'ensemble 1, GRU, norm layer / none'
         assert discrete or std_act in ops.STD_ACTS, std_act      # (read by continuous latents only, ref :515-519)
+        # the activation of _img_in, _ensemble_img_out and _obs_out (ref :339-351).  The batched observe, the C scans and the fused rollout
+        # have SiLU built in: an ELU block goes step by step through the per-layer nodes, as the norm-free layers do
+        self._act = _block_act(act)
         self.device = device
         self._embed_dim, self._action_dim, self._ensemble = embed_dim, action_dim, ensemble
         self._stoch, self._deter, self._hidden, self._discrete = stoch, deter, hidden, discrete
@@ -856,7 +868,7 @@ class EnsembleRSSM(Module):  # ref :302-555
 
     # ---- single steps (API parity; acting / data-free paths)
     def _prior_raw(self, deter):
-        x = _dense_ln_silu(deter, self._ensemble_img_out[0][0], self._ensemble_img_out[0][1])
+        x = _dense_ln_silu(deter, self._ensemble_img_out[0][0], self._ensemble_img_out[0][1], act=self._act)
         return ops.linear(x, self._ensemble_img_dist[0].weight, self._ensemble_img_dist[0].bias)
 
     def _prior_logits(self, deter):
@@ -865,9 +877,9 @@ class EnsembleRSSM(Module):  # ref :302-555
 
     def _post_raw(self, embed, deter=None):
         if self.single_obs_posterior:
-            x = _dense_ln_silu(embed, self._obs_out[0], self._obs_out[1])
+            x = _dense_ln_silu(embed, self._obs_out[0], self._obs_out[1], act=self._act)
         else:
-            x = _dense_ln_silu(deter, self._obs_out[0], self._obs_out[1], embed)
+            x = _dense_ln_silu(deter, self._obs_out[0], self._obs_out[1], embed, act=self._act)
         return ops.linear(x, self._obs_dist.weight, self._obs_dist.bias)
 
     def _post_logits(self, embed, deter=None):
@@ -885,7 +897,7 @@ class EnsembleRSSM(Module):  # ref :302-555
 
     def img_step(self, prev_state, prev_action, sample=True, site='rssm.prior', eps=None):
         """dense, GRU step, prior head, sample.  eps: the step's noise where a scan or a rollout drew it for all steps at once"""
-        x = _dense_ln_silu(self.get_stoch(prev_state), self._img_in[0], self._img_in[1], prev_action)
+        x = _dense_ln_silu(self.get_stoch(prev_state), self._img_in[0], self._img_in[1], prev_action, act=self._act)
         deter = ops.gru_step(x, prev_state['deter'], self._cell._layer.weight, self._cell._norm.weight,
                              self._cell._norm.bias)
         stoch, stats = self.get_stoch_stats_from_deter_state({'deter': deter}, sample, site, eps)
@@ -910,7 +922,7 @@ class EnsembleRSSM(Module):  # ref :302-555
         projection and the prior head are batched over all T steps; only h_{t-1} W_h + LN + gates is
         sequential (ops.gru_seq).  Without it, falls back to the step-by-step form."""
         B, T = action.shape[:2]
-        if not self._latent.fused:
+        if not self._latent.fused or self._act != 'SiLU':          # (the batched form and the scan have SiLU built in)
             return self._observe_stepwise(embed, action, is_first, state)
         if not self.single_obs_posterior:
             # (the scan's C launch loop has the LayerNorm launches of `norm: layer` built in: norm-free layers go step by step)
@@ -986,7 +998,7 @@ class EnsembleRSSM(Module):  # ref :302-555
         """ref :373-381: prior rollout for given actions (B,T,A)."""
         B, T = action.shape[:2]
         state = state if state is not None else self.initial(B)
-        if (self._latent.fused and not torch.is_grad_enabled() and action.is_cuda and self._norm != 'none'
+        if (self._latent.fused and not torch.is_grad_enabled() and action.is_cuda and self._norm != 'none' and self._act == 'SiLU'
                 and os.environ.get('GENRL_OBSERVE_SEQ', '1') != '0'):
             # forward only (the data-free block's warm-up rollouts, report, video_imagine all run under no_grad): the action half of
             # `_img_in` batched over T, the eight launches per step of the remaining chain from ONE host call (csrc/seq.hip)

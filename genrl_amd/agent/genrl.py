@@ -47,6 +47,11 @@ class GenRLAgent(DreamerAgent):
             if vec:
                 raise NotImplementedError(f'GenRLAgent is built on one image key: `{part}.mlp_keys` selects {vec}; vector observations '
                                           'are built for DreamerAgent and Plan2Explore')
+        for block in ('rssm', 'encoder', 'decoder', 'reward_head', 'actor', 'critic', 'connector_rssm'):
+            if cfg[block].get('act', 'SiLU') != 'SiLU':
+                raise NotImplementedError(f"GenRLAgent runs SiLU blocks: `{block}.act` is {cfg[block]['act']!r}; its connector, the batched "
+                                          "observe and the fused rollout have SiLU built in.  `act: ELU` is built for DreamerAgent and "
+                                          "Plan2Explore")
         super().__init__(**kwargs)
         self.n_frames = N_FRAMES
         assert self.cfg.batch_length % self.n_frames == 0, 'Fix batch length param'

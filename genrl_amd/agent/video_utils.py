@@ -71,6 +71,8 @@ class VideoSSM(common.EnsembleRSSM):
                  token_dropout=0., loss_scale=1, clip_add_noise=0, clip_lafite_noise=0, rescale_embeds=False,
                  denoising_ae=False, learn_initial=True, **kwargs):
         super().__init__(*args, **kwargs)
+        if self._act != 'SiLU':          # (the aligner, the action MLP and the teacher-forced prior below are SiLU layers)
+            raise NotImplementedError(f"the connector runs SiLU layers: `connector_rssm.act` is {self._act!r} (DESIGN 5n)")
         assert not temporal_embeds and token_dropout == 0 and detached_post and learn_initial, \
             'shipped connector configuration only (agent/genrl.yaml:15)'
         hidden, deter, norm, act_dim = kwargs['hidden'], kwargs['deter'], kwargs['norm'], kwargs['action_dim']

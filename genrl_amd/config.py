@@ -92,7 +92,7 @@ def dreamer_v2_settings():
     """What conf/defaults/dreamer_v2.yaml sets differently from dreamer_v3.yaml (config data, restated): norm-free RSSM / MLP layers,
     one-wide mse heads for reward and critic, a truncated-normal actor, a unit-variance image likelihood, KL balance 0.8 at scale 1, no
     return EMA (the reward goes through StreamNorm(**reward_norm) instead) and the v2 optimiser values.  `act: elu` is a comment in that
-    file: the activation stays SiLU.  `precision: 16` there is forced to 32 like everywhere in this module."""
+    file: the activation stays SiLU unless a block's override says `act='ELU'`.  `precision: 16` there is forced to 32 like everywhere in this module."""
     return dict(
         rssm=dict(ensemble=1, hidden=512, deter=512, stoch=32, discrete=32, norm='none', std_act='softplus', min_std=0.1,
                   single_obs_posterior=False),
@@ -113,7 +113,9 @@ def dreamer_cfg(batch_size=64, batch_length=50, device='cuda', task='walker_walk
     """conf/defaults/dreamer_v3.yaml (defaults='dreamer_v2': dreamer_v2.yaml, see dreamer_v2_settings) + conf/env/dmc_pixels.yaml +
     agent/dreamer.yaml (BASELINE configs[2]: DreamerAgent, walker A=6).  Overrides `discrete_actions=True` (one-hot actor head) and, with it,
     `actor_grad='reinforce'` select the discrete-action routes; both are passed through as given.  An `rssm` override with
-    `discrete=False` (and `stoch`, `std_act` in softplus / sigmoid / sigmoid2, `min_std`) selects continuous latents."""
+    `discrete=False` (and `stoch`, `std_act` in softplus / sigmoid / sigmoid2, `min_std`) selects continuous latents.
+    `act='ELU'` in an override of `rssm`, `encoder`, `decoder`, `reward_head`, `actor` or `critic` (the `# act: elu` of the reference's
+    files) gives that block ELU, each block on its own; any other name raises NotImplementedError at construction."""
     assert defaults in ('dreamer_v3', 'dreamer_v2'), defaults
     rssm = dict(ensemble=1, hidden=512, deter=512, stoch=32, discrete=32, norm='layer', std_act='softplus', min_std=0.1,
                 single_obs_posterior=False)

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
+#include "genrl_hip.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -172,6 +173,15 @@ __device__ __forceinline__ float dsiluf_(float x) {
   float s = sigmoidf_(x);
   return s * (1.0f + x * (1.0f - s));
 }
+// torch.nn.ELU (alpha 1) and its derivative from the pre-activation.  expm1f, not expf - 1: |z| of 1e-6 keeps its digits.  z = -100: y = -1,
+// dy/dz = 0 (expf underflows to 0); z = +100: y = z; both arms give 1 at z = 0; a NaN fails `z > 0` and goes through expm1f / expf as NaN
+__device__ __forceinline__ float eluf_(float z) { return z > 0.0f ? z : expm1f(z); }
+__device__ __forceinline__ float deluf_(float z) { return z > 0.0f ? 1.0f : expf(z); }
+// The activation behind a LayerNorm or a norm-free Linear, by its code in the C entries (include/genrl_hip.h GENRL_ACT_*): every
+// activation site of the row kernels and of the fused product epilogue calls this pair
+static inline bool bad_act_code(int act) { return act != GENRL_ACT_NONE && act != GENRL_ACT_SILU && act != GENRL_ACT_ELU; }
+__device__ __forceinline__ float act_apply(float z, int act) { return act == GENRL_ACT_SILU ? siluf_(z) : (act == GENRL_ACT_ELU ? eluf_(z) : z); }
+__device__ __forceinline__ float act_grad(float z, int act) { return act == GENRL_ACT_SILU ? dsiluf_(z) : (act == GENRL_ACT_ELU ? deluf_(z) : 1.0f); }
 // sign(x) log(|x| + 1) and its inverse: |x| + 1 is rounded to fp32 first, as the reference and the oracle do (no log1p)
 __device__ __forceinline__ float symlogf_(float x) { return copysignf(logf(fabsf(x) + 1.0f), x); }
 __device__ __forceinline__ float symexpf_(float x) { return copysignf(expf(fabsf(x)) - 1.0f, x); }

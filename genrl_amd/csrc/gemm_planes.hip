@@ -88,14 +88,14 @@ struct ConvGather {
 // atomic add, a poll with L2-served (sc1) loads, sc1 loads of the peers' records -- no fence, no cache write-back / invalidate, nothing
 // crosses the fabric (scripts/micro/xcd_barrier.hip, profiles/r06_xcd_barrier.txt: 0.71 us for 16 workgroups against 3.9 us chip-wide).
 // Every workgroup then normalises its own tile from registers and writes y as fp32 (optional) and as h2 planes with ONE scale for the
-// whole tensor, known from gamma / beta alone (|gamma x^ + beta| <= max|gamma| sqrt(N) + max|beta|, |SiLU z| <= |z|: no second exchange
+// whole tensor, known from gamma / beta alone (|gamma x^ + beta| <= max|gamma| sqrt(N) + max|beta|, |SiLU z|, |ELU z| <= |z|: no second exchange
 // for a row maximum; fp16 is a floating-point format, so elements down to 2^-25 of the bound keep all 22 bits).
 // slab of the exchange records for launches with tn column tiles per row block (floats): per-tn slabs keep the record tags of a row block's
 // slots in lockstep (every slot of a slab's row block takes part in exactly the same launches)
 __device__ __host__ __forceinline__ long ln_slab(int tn) { return (long)(tn - 1) * 65536; }
 struct LnEpi {
   const float* gamma; const float* beta;     // [N]; 16-byte aligned
-  float eps; int act;                        // act: 1 = SiLU
+  float eps; int act;                        // act: GENRL_ACT_* (0 none, 1 SiLU, 2 ELU)
   float* y; long ldy;                        // fp32 output rows (may be null: planes only)
   u16* yp; long yld, yplane; float* yinv;    // h2 planes of y (+ per-row inverse scale: the same value in every row)
   float* mean; float* rstd;                  // [M] row statistics (for the backward)
@@ -660,7 +660,7 @@ __device__ __forceinline__ void gemm_planes_body(PlaneSeg s0, PlaneSeg s1, float
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
           const float z = (o[4 * gq + v] - mu) * rs * g[v] + b[v];
-          y[v] = ln.act ? siluf_(z) : z;
+          y[v] = act_apply(z, ln.act);
         }
         if (ln.y) *reinterpret_cast<float4*>(ln.y + (long)row * ln.ldy + col) = make_float4(y[0], y[1], y[2], y[3]);
         if (ln.yp) {
@@ -2005,6 +2005,7 @@ int genrl_gemm_h2_ln(const uint16_t* a0, long a0_ld, long a0_plane, const float*
                      float* part, unsigned* sync, void* stream) {
   GENRL_ENTER();
   route_reset();
+  if (bad_act_code(act)) return GENRL_EINVAL;
   if (!genrl_gemm_h2_ln_ok(M, N) || k0 <= 0 || (k0 & 63) || (k1 & 63) || k1 < 0 || !gamma || !beta || !part || !sync || !C) return GENRL_EINVAL;
   if ((a0_ld & 7) || (b0_ld & 7) || (k1 && ((a1_ld & 7) || (b1_ld & 7))) || (ldc & 3) || (y && (ldy & 3)) || (yp && ((yld & 3) || !yinv))) return GENRL_EINVAL;
   if (((reinterpret_cast<uintptr_t>(C) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta) |

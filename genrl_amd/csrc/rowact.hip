@@ -1,5 +1,5 @@
 // Activations that stand alone between two products (gfx950), each with its backward: the ReLU between the two layers of a Plan2Explore
-// ensemble member (agent/plan2explore.py:8-41) and the SiLU behind a norm-free Linear (`norm: none`, agent/dreamer_utils.py:739-747).
+// ensemble member (agent/plan2explore.py:8-41) and the SiLU or ELU behind a norm-free Linear (`norm: none`, agent/dreamer_utils.py:739-747).
 //
 // HBM-bound streams over rows of any multiple of 4 floats: one 256-thread workgroup walks rows grid-strided with 16-byte accesses.  A call
 // that also emits h2 planes needs the row maximum before it can split, so it makes two sweeps over the row: the first computes and stores
@@ -21,6 +21,10 @@ struct Relu {          // saved: the output y.  (a NaN stays NaN, as in torch.re
 struct Silu {          // saved: the pre-activation x.  x = -100: exp(100) = inf, sigmoid = 0, y = -0; a NaN stays NaN
   static __device__ __forceinline__ float fwd(float x) { return siluf_(x); }
   static __device__ __forceinline__ float bwd(float g, float x) { return g * dsiluf_(x); }
+};
+struct Elu {           // saved: the pre-activation x.  x = -100: y = -1, dy/dx = 0; a NaN stays NaN (common.h)
+  static __device__ __forceinline__ float fwd(float x) { return eluf_(x); }
+  static __device__ __forceinline__ float bwd(float g, float x) { return g * deluf_(x); }
 };
 
 // y = act(x) (y may be x itself)
@@ -112,6 +116,16 @@ int genrl_silu_fwd_h2(const float* x, long ldx, float* y, long ldy, int M, int N
 int genrl_silu_bwd_h2(const float* dy, long lddy, const float* x, long ldx, float* dx, long lddx, int M, int N, uint16_t* dxp, long ldp,
                       long plane, float* inv, void* stream) {
   return act_bwd<Silu>(dy, lddy, x, ldx, dx, lddx, M, N, dxp, ldp, plane, inv, stream);
+}
+
+int genrl_elu_fwd_h2(const float* x, long ldx, float* y, long ldy, int M, int N, uint16_t* yp, long ldp, long plane, float* inv,
+                     void* stream) {
+  return act_fwd<Elu>(x, ldx, y, ldy, M, N, yp, ldp, plane, inv, stream);
+}
+
+int genrl_elu_bwd_h2(const float* dy, long lddy, const float* x, long ldx, float* dx, long lddx, int M, int N, uint16_t* dxp, long ldp,
+                     long plane, float* inv, void* stream) {
+  return act_bwd<Elu>(dy, lddy, x, ldx, dx, lddx, M, N, dxp, ldp, plane, inv, stream);
 }
 
 }  // extern "C"

@@ -11,9 +11,9 @@
 
 namespace {
 
-// ------------------------------------------------------------------ LayerNorm (+SiLU) forward
+// ------------------------------------------------------------------ LayerNorm (+SiLU / ELU) forward
 // y = act(LN(x) * gamma + beta); saves mean / rstd per row.  ref: nn.LayerNorm after nn.Linear
-// (agent/dreamer_utils.py:844-859) + SiLU (:462-463, :745).
+// (agent/dreamer_utils.py:844-859) + the block's `act` (:462-463, :745): act_apply / act_grad (common.h) by its GENRL_ACT_* code.
 __global__ __launch_bounds__(256) void ln_act_fwd_kernel(const float* __restrict__ x, long ldx,
                                                          const float* __restrict__ gamma,
                                                          const float* __restrict__ beta,
@@ -25,8 +25,16 @@ __global__ __launch_bounds__(256) void ln_act_fwd_kernel(const float* __restrict
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
   const float* xr = x + (long)row * ldx;
-  float s = 0.f;
-  for (int j = lane; j < N; j += 64) s += xr[j];
+  // (compensated on rows beyond the fast kernels' 4096 floats, which only this kernel takes: a lane adds N / 64 values one after the other,
+  // and on a row of equal values every rounding falls the same way -- 4.7 2^-24 of the mean at N = 6000, which rstd then multiplies into a
+  // zero-variance row.  Every shorter row adds as it always did: comp stays 0 and t is xr[j] itself)
+  const bool long_row = N > 4096;
+  float s = 0.f, comp = 0.f;
+  for (int j = lane; j < N; j += 64) {
+    const float t = xr[j] - comp, u = s + t;
+    if (long_row) comp = (u - s) - t;
+    s = u;
+  }
   const float mean = wave_sum(s) / N;
   float v = 0.f;
   for (int j = lane; j < N; j += 64) {
@@ -37,7 +45,7 @@ __global__ __launch_bounds__(256) void ln_act_fwd_kernel(const float* __restrict
   float* yr = y + (long)row * ldy;
   for (int j = lane; j < N; j += 64) {
     float z = (xr[j] - mean) * rstd * gamma[j] + beta[j];
-    yr[j] = act ? siluf_(z) : z;
+    yr[j] = act_apply(z, act);
   }
   if (lane == 0) {
     mean_out[row] = mean;
@@ -60,7 +68,7 @@ __global__ __launch_bounds__(256) void ln_act_bwd_dx_kernel(
   for (int j = lane; j < N; j += 64) {
     const float xh = (xr[j] - mean) * rstd;
     float dz = dyr[j];
-    if (act) dz *= dsiluf_(xh * gamma[j] + beta[j]);
+    if (act) dz *= act_grad(xh * gamma[j] + beta[j], act);
     const float dxh = dz * gamma[j];
     s1 += dxh;
     s2 += dxh * xh;
@@ -71,7 +79,7 @@ __global__ __launch_bounds__(256) void ln_act_bwd_dx_kernel(
   for (int j = lane; j < N; j += 64) {
     const float xh = (xr[j] - mean) * rstd;
     float dz = dyr[j];
-    if (act) dz *= dsiluf_(xh * gamma[j] + beta[j]);
+    if (act) dz *= act_grad(xh * gamma[j] + beta[j], act);
     dxr[j] = rstd * (dz * gamma[j] - s1 - xh * s2);
   }
 }
@@ -94,7 +102,7 @@ __global__ __launch_bounds__(256) void ln_act_bwd_params_kernel(
     for (int r = r0 + sub; r < r1; r += 4) {
       const float xh = (x[(long)r * ldx + c] - mean_in[r]) * rstd_in[r];
       float dz = dy[(long)r * lddy + c];
-      if (act) dz *= dsiluf_(xh * g + b);
+      if (act) dz *= act_grad(xh * g + b, act);
       ag += dz * xh;
       ab += dz;
     }
@@ -119,7 +127,7 @@ __global__ __launch_bounds__(256) void ln_act_bwd_params_kernel(
 __device__ __forceinline__ float4 ld4z(const float* p, bool ok) {
   return ok ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
-template <int GL>
+template <int GL, int ACT>
 __global__ __launch_bounds__(256) void ln_act_fwd_grp_kernel(const float* __restrict__ x, long ldx,
                                                              const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, float* __restrict__ y,
@@ -134,7 +142,7 @@ __global__ __launch_bounds__(256) void ln_act_fwd_grp_kernel(const float* __rest
   const float4 g4 = ld4z(gamma + c, cok), b4 = ld4z(beta + c, cok);
   const float invn = 1.0f / N;
   // UNIFORM-scale plane copy of the output (xo.p != null): |x^| <= sqrt(N - 1) for every element of a normalised row, so
-  // |gamma x^ + beta| <= max|gamma| sqrt(N) + max|beta| =: bound, and |SiLU(z)| <= |z|: ONE power-of-two scale fits the whole
+  // |gamma x^ + beta| <= max|gamma| sqrt(N) + max|beta| =: bound, and |SiLU(z)|, |ELU(z)| <= |z|: ONE power-of-two scale fits the whole
   // tensor, known from the parameters alone (every lane group holds all of gamma / beta: same value everywhere), no overflow
   // possible.  A uniform scale is what lets the conv products gather patches across pixel rows (csrc/gemm_planes.hip).
   float u_inv = 0.f, u_sc = 0.f;
@@ -152,7 +160,7 @@ __global__ __launch_bounds__(256) void ln_act_fwd_grp_kernel(const float* __rest
     const float rstd = 1.0f / sqrtf(var + eps);
     float4 z = make_float4(d.x * rstd * g4.x + b4.x, d.y * rstd * g4.y + b4.y, d.z * rstd * g4.z + b4.z,
                            d.w * rstd * g4.w + b4.w);
-    if (act) z = make_float4(siluf_(z.x), siluf_(z.y), siluf_(z.z), siluf_(z.w));
+    if (act) z = make_float4(act_apply(z.x, ACT), act_apply(z.y, ACT), act_apply(z.z, ACT), act_apply(z.w, ACT));
     if (cok && y) *reinterpret_cast<float4*>(y + r * ldy + c) = z;            // (y == NULL: planes only)
     if (xo.p && c < xo.ld) h2_store4(xo, r, c, cok ? z : make_float4(0.f, 0.f, 0.f, 0.f), u_sc);     // (padding columns: zeros)
     if (gl == 0) {
@@ -164,7 +172,7 @@ __global__ __launch_bounds__(256) void ln_act_fwd_grp_kernel(const float* __rest
 }
 
 // part layout [gridDim.x][np][N] (np = 2: dgamma, dbeta; 3: + column sums of dx), or NULL
-template <int GL>
+template <int GL, int ACT>
 __global__ __launch_bounds__(256) void ln_act_bwd_grp_kernel(const float* __restrict__ dy, long lddy,
                                                              const float* __restrict__ x, long ldx,
                                                              const float* __restrict__ gamma,
@@ -191,10 +199,10 @@ __global__ __launch_bounds__(256) void ln_act_bwd_grp_kernel(const float* __rest
     if (!cok) xh = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 dz = dv;
     if (act) {
-      dz.x *= dsiluf_(xh.x * g4.x + b4.x);
-      dz.y *= dsiluf_(xh.y * g4.y + b4.y);
-      dz.z *= dsiluf_(xh.z * g4.z + b4.z);
-      dz.w *= dsiluf_(xh.w * g4.w + b4.w);
+      dz.x *= act_grad(xh.x * g4.x + b4.x, ACT);
+      dz.y *= act_grad(xh.y * g4.y + b4.y, ACT);
+      dz.z *= act_grad(xh.z * g4.z + b4.z, ACT);
+      dz.w *= act_grad(xh.w * g4.w + b4.w, ACT);
     }
     const float4 dxh = make_float4(dz.x * g4.x, dz.y * g4.y, dz.z * g4.z, dz.w * g4.w);
     const float s1 = group_sum<GL>(dxh.x + dxh.y + dxh.z + dxh.w) * invn;
@@ -570,7 +578,7 @@ __device__ __forceinline__ Sum2 block_sum2_256(float a, float b, float* red /* >
   return r;
 }
 
-template <int NV>
+template <int NV, int ACT>
 __global__ __launch_bounds__(256) void ln_act_fwd_blk_kernel(const float* __restrict__ x, long ldx,
                                                              const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, float* __restrict__ y,
@@ -612,7 +620,7 @@ __global__ __launch_bounds__(256) void ln_act_fwd_blk_kernel(const float* __rest
         o.z = (v[i].z - mean) * rstd * g.z + b.z;
         o.w = (v[i].w - mean) * rstd * g.w + b.w;
         if (act) {
-          o.x = siluf_(o.x); o.y = siluf_(o.y); o.z = siluf_(o.z); o.w = siluf_(o.w);
+          o.x = act_apply(o.x, ACT); o.y = act_apply(o.y, ACT); o.z = act_apply(o.z, ACT); o.w = act_apply(o.w, ACT);
         }
         if (y) yr[j] = o;            // (y == NULL: planes only -- a caller whose every consumer reads the planes)
         v[i] = o;
@@ -640,7 +648,7 @@ __global__ __launch_bounds__(256) void ln_act_fwd_blk_kernel(const float* __rest
 // dx (may alias dy) + per-workgroup partials part[blockIdx.x][NP][N] (if part != null):
 // NP = 2: (dgamma, dbeta);  NP = 3: (dgamma, dbeta, column sums of dx = the bias gradient of the
 // Linear layer that produced x).
-template <int NV>
+template <int NV, int ACT>
 __global__ __launch_bounds__(256) void ln_act_bwd_blk_kernel(const float* dy, long lddy, const float* __restrict__ x,
                                                              long ldx, const float* __restrict__ gamma,
                                                              const float* __restrict__ beta,
@@ -675,8 +683,8 @@ __global__ __launch_bounds__(256) void ln_act_bwd_blk_kernel(const float* dy, lo
         float4 h;
         h.x = (xv.x - mean) * rstd; h.y = (xv.y - mean) * rstd; h.z = (xv.z - mean) * rstd; h.w = (xv.w - mean) * rstd;
         if (act) {
-          d.x *= dsiluf_(h.x * g[i].x + b[i].x); d.y *= dsiluf_(h.y * g[i].y + b[i].y);
-          d.z *= dsiluf_(h.z * g[i].z + b[i].z); d.w *= dsiluf_(h.w * g[i].w + b[i].w);
+          d.x *= act_grad(h.x * g[i].x + b[i].x, ACT); d.y *= act_grad(h.y * g[i].y + b[i].y, ACT);
+          d.z *= act_grad(h.z * g[i].z + b[i].z, ACT); d.w *= act_grad(h.w * g[i].w + b[i].w, ACT);
         }
         xh[i] = h; dz[i] = d;
         ag[i].x += d.x * h.x; ag[i].y += d.y * h.y; ag[i].z += d.z * h.z; ag[i].w += d.w * h.w;
@@ -742,7 +750,7 @@ __global__ __launch_bounds__(256) void ln_act_bwd_blk_kernel(const float* dy, lo
 // of loads outstanding.  The block-per-row kernels above pay two __syncthreads pairs per row and hold one float4 per
 // thread: at M = 16384 rows they ran at ~1.2 TB/s (246 us for the policy's batched backward); the parameter-gradient
 // partials of the four waves are summed through LDS once per workgroup.
-template <int NV>
+template <int NV, int ACT>
 __global__ __launch_bounds__(256) void ln_act_fwd_wave_kernel(const float* __restrict__ x, long ldx,
                                                               const float* __restrict__ gamma,
                                                               const float* __restrict__ beta, float* __restrict__ y,
@@ -789,7 +797,7 @@ __global__ __launch_bounds__(256) void ln_act_fwd_wave_kernel(const float* __res
         o.z = (v[i].z - mean) * rstd * g[i].z + b[i].z;
         o.w = (v[i].w - mean) * rstd * g[i].w + b[i].w;
         if (act) {
-          o.x = siluf_(o.x); o.y = siluf_(o.y); o.z = siluf_(o.z); o.w = siluf_(o.w);
+          o.x = act_apply(o.x, ACT); o.y = act_apply(o.y, ACT); o.z = act_apply(o.z, ACT); o.w = act_apply(o.w, ACT);
         }
         if (y) yr[j] = o;            // (y == NULL: planes only)
         v[i] = o;
@@ -891,7 +899,7 @@ __global__ __launch_bounds__(64) void onehot_gather_ln_kernel(const int* __restr
 
 // backward: dx (may alias dy) + per-workgroup partials part[blockIdx.x][np][N] (np = 2: dgamma, dbeta; 3: + column
 // sums of dx), same contract as ln_act_bwd_blk_kernel
-template <int NV>
+template <int NV, int ACT>
 __global__ __launch_bounds__(256) void ln_act_bwd_wave_kernel(const float* dy, long lddy, const float* __restrict__ x,
                                                               long ldx, const float* __restrict__ gamma,
                                                               const float* __restrict__ beta,
@@ -945,8 +953,8 @@ __global__ __launch_bounds__(256) void ln_act_bwd_wave_kernel(const float* dy, l
         float4 h;
         h.x = (xv.x - mean) * rstd; h.y = (xv.y - mean) * rstd; h.z = (xv.z - mean) * rstd; h.w = (xv.w - mean) * rstd;
         if (act) {
-          d.x *= dsiluf_(h.x * g[i].x + b[i].x); d.y *= dsiluf_(h.y * g[i].y + b[i].y);
-          d.z *= dsiluf_(h.z * g[i].z + b[i].z); d.w *= dsiluf_(h.w * g[i].w + b[i].w);
+          d.x *= act_grad(h.x * g[i].x + b[i].x, ACT); d.y *= act_grad(h.y * g[i].y + b[i].y, ACT);
+          d.z *= act_grad(h.z * g[i].z + b[i].z, ACT); d.w *= act_grad(h.w * g[i].w + b[i].w, ACT);
         }
         xh[i] = h; dz[i] = d;
         ag[i].x += d.x * h.x; ag[i].y += d.y * h.y; ag[i].z += d.z * h.z; ag[i].w += d.w * h.w;
@@ -1327,9 +1335,20 @@ static int split_after(const float* y, long ldy, int M, int N, const PlaneOut& x
   return genrl_split_h2(y, ldy, M, N, xo.p, xo.ld, xo.plane, xo.inv, 0, stream);
 }
 
+// KERNEL<NV, ACT>(...) on 256-thread workgroups with ACT, the activation a nonzero `act` argument applies, as a template parameter: SiLU
+// for act 0 / 1 -- that instantiation is the kernel as it was, argument for argument -- and ELU for act 2.  A third runtime arm cost the
+// wave-per-row kernels 11 % (forward) and 12 % (backward) at N = 1024 on an MI355X; the lane-group, wave and block kernels
+// are launched this way, the generic ones pick the arm from the argument
+#define LAUNCH_ACT(KERNEL, NV, ACT, GRID, S, ...)                                                                                  \
+  do {                                                                                                                              \
+    if ((ACT) == GENRL_ACT_ELU) hipLaunchKernelGGL((KERNEL<NV, GENRL_ACT_ELU>), dim3(GRID), dim3(256), 0, S, __VA_ARGS__);          \
+    else hipLaunchKernelGGL((KERNEL<NV, GENRL_ACT_SILU>), dim3(GRID), dim3(256), 0, S, __VA_ARGS__);                                \
+  } while (0)
+
 static int ln_act_fwd_impl(const float* x, long ldx, const float* gamma, const float* beta, float* y, long ldy,
                      float* mean, float* rstd, int M, int N, float eps, int act, PlaneOut xo, void* stream, bool uniform = false) {
   GENRL_ENTER();
+  if (bad_act_code(act)) return GENRL_EINVAL;
   if (M <= 0) return GENRL_OK;
   if (xo.p && (!xo.inv || (xo.ld & 3) || xo.ld < N)) return GENRL_EINVAL;
   hipStream_t s = (hipStream_t)stream;
@@ -1343,7 +1362,7 @@ static int ln_act_fwd_impl(const float* x, long ldx, const float* gamma, const f
     const int gl = N <= 64 ? 16 : (N <= 128 ? 32 : 64);
     const int grid = (int)std::min<long>(cdiv(M, 4 * (64 / gl)), 2048);
     const PlaneOut xu = uniform ? xo : PlaneOut{nullptr, 0, 0, nullptr};
-#define GO(GLV) hipLaunchKernelGGL((ln_act_fwd_grp_kernel<GLV>), dim3(grid), dim3(256), 0, s, x, ldx, gamma, beta, y, ldy, mean, rstd, M, N, eps, act, xu)
+#define GO(GLV) LAUNCH_ACT(ln_act_fwd_grp_kernel, GLV, act, grid, s, x, ldx, gamma, beta, y, ldy, mean, rstd, M, N, eps, act, xu)
     if (gl == 16) GO(16); else if (gl == 32) GO(32); else GO(64);
 #undef GO
     if (uniform) { GENRL_CHECK_LAUNCH(); return GENRL_OK; }
@@ -1352,7 +1371,7 @@ static int ln_act_fwd_impl(const float* x, long ldx, const float* gamma, const f
   } else if (fast && N <= 1024) {
     const int grid = (int)std::min<long>(cdiv(M, 4), 4 * BLK_GRID);
     const int nv = cdiv(N, 256);
-#define GO(NV) hipLaunchKernelGGL((ln_act_fwd_wave_kernel<NV>), dim3(grid), dim3(256), 0, s, x, ldx, gamma, beta, y, ldy, mean, rstd, M, N, eps, act, xo)
+#define GO(NV) LAUNCH_ACT(ln_act_fwd_wave_kernel, NV, act, grid, s, x, ldx, gamma, beta, y, ldy, mean, rstd, M, N, eps, act, xo)
     if (nv == 2) GO(2); else if (nv == 3) GO(3); else GO(4);
 #undef GO
     GENRL_CHECK_LAUNCH();
@@ -1360,7 +1379,7 @@ static int ln_act_fwd_impl(const float* x, long ldx, const float* gamma, const f
   } else if (fast) {
     const int grid = M < 4 * BLK_GRID ? M : 4 * BLK_GRID;
     const int nv = cdiv(N, 1024);
-#define GO(NV) hipLaunchKernelGGL((ln_act_fwd_blk_kernel<NV>), dim3(grid), dim3(256), 0, s, x, ldx, gamma, beta, y, ldy, mean, rstd, M, N, eps, act, xo)
+#define GO(NV) LAUNCH_ACT(ln_act_fwd_blk_kernel, NV, act, grid, s, x, ldx, gamma, beta, y, ldy, mean, rstd, M, N, eps, act, xo)
     if (nv == 1) GO(1); else if (nv == 2) GO(2); else if (nv == 3) GO(3); else GO(4);
 #undef GO
     GENRL_CHECK_LAUNCH();
@@ -1467,6 +1486,7 @@ static int ln_act_bwd_impl(const float* dy, long lddy, const float* x, long ldx,
                      float* dgamma, float* dbeta, float* dcolsum, float* ws, int M, int N, int act,
                      int accumulate_params, PlaneOut xo, void* stream, float* amax_ws = nullptr) {
   GENRL_ENTER();
+  if (bad_act_code(act)) return GENRL_EINVAL;
   if (M <= 0) return GENRL_OK;
   if (amax_ws && !(N <= 256 && M >= 64)) return GENRL_EINVAL;      // (uniform planes: the channel-LayerNorm kernel only)
   if (xo.p && (!xo.inv || (xo.ld & 3) || xo.ld < N)) return GENRL_EINVAL;
@@ -1488,7 +1508,7 @@ static int ln_act_bwd_impl(const float* dy, long lddy, const float* x, long ldx,
     const int grid = narrow_grid_for(M, gl);
     float* part = dgamma ? ws : nullptr;
     const int np = dcolsum ? 3 : 2;
-#define GO(GLV) hipLaunchKernelGGL((ln_act_bwd_grp_kernel<GLV>), dim3(grid), dim3(256), 0, s, dy, lddy, x, ldx, gamma, beta, mean, rstd, dx, lddx, part, M, N, act, np, amax_ws)
+#define GO(GLV) LAUNCH_ACT(ln_act_bwd_grp_kernel, GLV, act, grid, s, dy, lddy, x, ldx, gamma, beta, mean, rstd, dx, lddx, part, M, N, act, np, amax_ws)
     if (gl == 16) GO(16); else if (gl == 32) GO(32); else GO(64);
 #undef GO
     if (dgamma && !defer) reduce_params(ws, ws + (long)grid * np * N, dgamma, dbeta, grid, N, accumulate_params, s, dcolsum);
@@ -1501,7 +1521,7 @@ static int ln_act_bwd_impl(const float* dy, long lddy, const float* x, long ldx,
     const int nv = cdiv(N, 256);
     float* part = dgamma ? ws : nullptr;
     const int np = dcolsum ? 3 : 2;
-#define GO(NV) hipLaunchKernelGGL((ln_act_bwd_wave_kernel<NV>), dim3(grid), dim3(256), 0, s, dy, lddy, x, ldx, gamma, beta, mean, rstd, dx, lddx, part, M, N, act, np, xo)
+#define GO(NV) LAUNCH_ACT(ln_act_bwd_wave_kernel, NV, act, grid, s, dy, lddy, x, ldx, gamma, beta, mean, rstd, dx, lddx, part, M, N, act, np, xo)
     if (nv == 2) GO(2); else if (nv == 3) GO(3); else GO(4);
 #undef GO
     if (dgamma && !defer) reduce_params(ws, ws + (long)grid * np * N, dgamma, dbeta, grid, N, accumulate_params, s, dcolsum);
@@ -1513,7 +1533,7 @@ static int ln_act_bwd_impl(const float* dy, long lddy, const float* x, long ldx,
     const int nv = cdiv(N, 1024);
     float* part = dgamma ? ws : nullptr;
     const int np = dcolsum ? 3 : 2;
-#define GO(NV) hipLaunchKernelGGL((ln_act_bwd_blk_kernel<NV>), dim3(grid), dim3(256), 0, s, dy, lddy, x, ldx, gamma, beta, mean, rstd, dx, lddx, part, M, N, act, np, xo)
+#define GO(NV) LAUNCH_ACT(ln_act_bwd_blk_kernel, NV, act, grid, s, dy, lddy, x, ldx, gamma, beta, mean, rstd, dx, lddx, part, M, N, act, np, xo)
     if (nv == 1) GO(1); else if (nv == 2) GO(2); else if (nv == 3) GO(3); else GO(4);
 #undef GO
     if (dgamma && !defer) reduce_params(ws, ws + (long)grid * np * N, dgamma, dbeta, grid, N, accumulate_params, s, dcolsum);

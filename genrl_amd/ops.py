@@ -367,7 +367,38 @@ def linear(x, W, b=None):
     return _Linear.apply(x, W, b)
 
 
-# ------------------------------------------------------------------ LayerNorm (+SiLU)
+# ------------------------------------------------------------------ LayerNorm (+SiLU / ELU)
+
+# the `act:` of a network block (conf/defaults/*.yaml: SiLU, with `# act: elu` beside it) -> its GENRL_ACT_* code in the C entries
+# (include/genrl_hip.h).  The one table: the modules validate a name through act_code, the nodes below hand the code to the kernels.
+ACTS = {'SiLU': 1, 'ELU': 2}
+
+
+def act_code(act):
+    """'SiLU' / 'ELU' -> 1 / 2 (any other name: NotImplementedError(name), as the reference's get_act); a bool or a code passes
+    (ln_act's act=False: the LayerNorm alone)"""
+    if isinstance(act, str):
+        if act not in ACTS:
+            raise NotImplementedError(act)
+        return ACTS[act]
+    act = int(act)
+    if act not in (0, 1, 2):
+        raise NotImplementedError(act)
+    return act
+
+
+def act_layer_code(act):
+    """act_code for a layer that IS its activation (a norm-free Linear + act, a trunk of Dense -> LayerNorm -> act): SiLU or ELU, not 0"""
+    code = act_code(act)
+    if code == 0:
+        raise NotImplementedError('a dense layer without an activation: use ops.linear (+ ops.ln_act(..., act=False))')
+    return code
+
+
+def _ln_code(ln):
+    """the activation code of a conv layer's fused channel-LayerNorm: ln = (gamma, beta, eps) is SiLU, (gamma, beta, eps, act) says"""
+    return act_layer_code(ln[3]) if len(ln) > 3 else 1
+
 
 class _LNAct(Function):
     @staticmethod
@@ -399,8 +430,9 @@ class _LNAct(Function):
         return (dx.reshape(ctx.xshape) if dx is not None else None), dg, db, None, None
 
 
-def ln_act(x, gamma, beta, eps=1e-5, act=True):
-    return _LNAct.apply(x, gamma, beta, float(eps), int(act))
+def ln_act(x, gamma, beta, eps=1e-5, act='SiLU'):
+    """act: 'SiLU' (True) / 'ELU', or False: the LayerNorm alone"""
+    return _LNAct.apply(x, gamma, beta, float(eps), act_code(act))
 
 
 # ------------------------------------------------------------------ GRU gates
@@ -1462,16 +1494,16 @@ def _col2im(cols, bias, Nimg, Ha, Wa, C, k, Ho=0, Wo=0, nchw=False):
     return out
 
 
-def _ln_fwd_rows(pre2d, gamma, beta, eps):
+def _ln_fwd_rows(pre2d, gamma, beta, eps, act=1):
     M, N = pre2d.shape
     y = torch.empty_like(pre2d)
     mean = torch.empty(M, device=pre2d.device); rstd = torch.empty(M, device=pre2d.device)
-    check(lib().genrl_ln_act_fwd(_p(pre2d), N, _p(gamma), _p(beta), _p(y), N, _p(mean), _p(rstd), M, N, eps, 1,
+    check(lib().genrl_ln_act_fwd(_p(pre2d), N, _p(gamma), _p(beta), _p(y), N, _p(mean), _p(rstd), M, N, eps, act,
                                  _stream()), 'ln_act_fwd')
     return y, mean, rstd
 
 
-def _ln_bwd_rows(dy2d, pre2d, gamma, beta, mean, rstd, bias=None):
+def _ln_bwd_rows(dy2d, pre2d, gamma, beta, mean, rstd, bias=None, act=1):
     """-> dpre, dgamma, dbeta, column sums of dpre (= the producing layer's bias gradient), one pass.  When gamma,
     beta (and the layer's `bias`) have flat gradient buffers the three sums are accumulated straight into them and
     returned as None (nothing left for autograd to add)."""
@@ -1479,7 +1511,7 @@ def _ln_bwd_rows(dy2d, pre2d, gamma, beta, mean, rstd, bias=None):
     dpre = torch.empty_like(pre2d)
     g0, g1, g2, ws, acc_p, direct = _ln_param_targets(M, N, gamma, beta, bias, pre2d.device)
     check(lib().genrl_ln_act_bwd(_p(dy2d), N, _p(pre2d), N, _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dpre), N,
-                                 _p(g0), _p(g1), _p(g2), _p(ws), M, N, 1, acc_p, _stream()), 'ln_act_bwd')
+                                 _p(g0), _p(g1), _p(g2), _p(ws), M, N, act, acc_p, _stream()), 'ln_act_bwd')
     return (dpre, None, None, None) if direct else (dpre, g0, g1, g2)
 
 
@@ -1492,7 +1524,7 @@ class _Conv2dS2(Function):
     """nn.Conv2d(k, stride 2) as patch-gather + GEMM.  x: f32 NHWC (N,H,W,C) or u8 NCHW (N,C,H,W)
     [preprocess fused]; Wp (Co, k*k*Ci) = weight permuted to (co, kh, kw, ci); returns NHWC."""
     @staticmethod
-    def forward(ctx, x, Wp, b, k, gamma=None, beta=None, eps=0.0):
+    def forward(ctx, x, Wp, b, k, gamma=None, beta=None, eps=0.0, act=1):
         u8 = x.dtype == torch.uint8
         x = x.contiguous()
         if u8:
@@ -1511,8 +1543,9 @@ class _Conv2dS2(Function):
         ctx.dims = (Nimg, Hi, Wi, C, k, u8)
         ctx.fused_ln = gamma is not None
         ctx.bias = b
-        if ctx.fused_ln:           # channel-LayerNorm + SiLU of the layer (ImgChLayerNorm + act)
-            out, mean, rstd = _ln_fwd_rows(y, gamma, beta, eps)
+        ctx.act = act
+        if ctx.fused_ln:           # channel-LayerNorm + SiLU / ELU of the layer (ImgChLayerNorm + act)
+            out, mean, rstd = _ln_fwd_rows(y, gamma, beta, eps, act)
             ctx.save_for_backward(x, Wp, y, mean, rstd, gamma, beta)
             return out.reshape(Nimg, Ho, Wo, Co)
         ctx.save_for_backward(x, Wp)
@@ -1530,7 +1563,7 @@ class _Conv2dS2(Function):
         dx = dW = db = dg = dbe = None
         if ctx.fused_ln:
             pre, mean, rstd, gamma, beta = ctx.saved_tensors[2:]
-            dy2, dg, dbe, db_ln = _ln_bwd_rows(dy2, pre, gamma, beta, mean, rstd, ctx.bias)
+            dy2, dg, dbe, db_ln = _ln_bwd_rows(dy2, pre, gamma, beta, mean, rstd, ctx.bias, ctx.act)
         if ctx.needs_input_grad[1]:
             dW = torch.empty(Co, K, device=dy.device)
             if _implicit_conv(x, C) and Co % 4 == 0:
@@ -1545,7 +1578,7 @@ class _Conv2dS2(Function):
             dcols = torch.empty(M, K, device=dy.device)
             sgemm(dy2, Co, 1, Wp, 1, K, dcols, K, None, M, K, Co)     # dcols = dy W
             dx = _col2im(dcols, None, Nimg, Ho, Wo, C, k, Hi, Wi)
-        return dx, dW, db, None, dg, dbe, None
+        return dx, dW, db, None, dg, dbe, None, None
 
 
 def permuted(W):
@@ -1578,12 +1611,12 @@ class _PermuteWeight(Function):
 
 def conv2d_s2(x, W, b, ln=None, fp32_out=True, planes_out=True):
     """W (Co,Ci,k,k) in the reference layout; permuted per call to (Co, kh*kw*Ci) (gradient flows back
-    through the permute).  ln = (gamma, beta, eps): channel-LayerNorm + SiLU fused into the same node."""
+    through the permute).  ln = (gamma, beta, eps[, act]): channel-LayerNorm + SiLU (act 'ELU': ELU) fused into the same node."""
     Co, Ci, k, _ = W.shape
     Wp = _PermuteWeight.apply(W).reshape(Co, k * k * Ci)
     if ln is None:
         return _Conv2dS2.apply(x, Wp, b, k)
-    return _Conv2dS2.apply(x, Wp, b, k, ln[0], ln[1], float(ln[2]))
+    return _Conv2dS2.apply(x, Wp, b, k, ln[0], ln[1], float(ln[2]), _ln_code(ln))
 
 
 CONVT_DIRECT = os.environ.get('GENRL_CONVT_DIRECT', '1') != '0'
@@ -1607,7 +1640,7 @@ class _ConvT2dS2(Function):
     """nn.ConvTranspose2d(k, stride 2) as GEMM + gather-form col2im.  x NHWC (N,Hi,Wi,Ci);
     Wp (Ci, k*k*Co) = weight permuted to (ci, kh, kw, co); returns NHWC."""
     @staticmethod
-    def forward(ctx, x, Wp, b, k, gamma=None, beta=None, eps=0.0, out_nchw=False):
+    def forward(ctx, x, Wp, b, k, gamma=None, beta=None, eps=0.0, out_nchw=False, act=1):
         x = _f32(x).contiguous()
         Nimg, Hi, Wi, Ci = x.shape
         Nw = Wp.shape[1]
@@ -1630,8 +1663,9 @@ class _ConvT2dS2(Function):
         ctx.dims = (Nimg, Hi, Wi, Ci, Co, k)
         ctx.fused_ln = gamma is not None
         ctx.bias = b
+        ctx.act = act
         if ctx.fused_ln:
-            out, mean, rstd = _ln_fwd_rows(y.reshape(-1, Co), gamma, beta, eps)
+            out, mean, rstd = _ln_fwd_rows(y.reshape(-1, Co), gamma, beta, eps, act)
             ctx.save_for_backward(x, Wp, y, mean, rstd, gamma, beta)
             return out.reshape(y.shape)
         ctx.save_for_backward(x, Wp)
@@ -1647,7 +1681,7 @@ class _ConvT2dS2(Function):
         dg = dbe = db_ln = None
         if ctx.fused_ln:
             pre, mean, rstd, gamma, beta = ctx.saved_tensors[2:]
-            dy, dg, dbe, db_ln = _ln_bwd_rows(dy.reshape(-1, Co), pre.reshape(-1, Co), gamma, beta, mean, rstd, ctx.bias)
+            dy, dg, dbe, db_ln = _ln_bwd_rows(dy.reshape(-1, Co), pre.reshape(-1, Co), gamma, beta, mean, rstd, ctx.bias, ctx.act)
             dy = dy.reshape(Nimg, Ho, Wo, Co)
         implicit = _implicit_conv(dy, Co) and Ci % 4 == 0 and not ctx.out_nchw
         dx = dW = db = None
@@ -1688,7 +1722,7 @@ class _ConvT2dS2(Function):
                 db = _nchw_bias_grad(dy, ctx.bias)
             else:
                 db = colsum(dy.reshape(-1, Co))
-        return dx, dW, db, None, dg, dbe, None, None
+        return dx, dW, db, None, dg, dbe, None, None, None
 
 
 def convT2d_s2(x, W, b, ln=None, out_nchw=False, fp32_out=True, planes_out=True):
@@ -1698,7 +1732,7 @@ def convT2d_s2(x, W, b, ln=None, out_nchw=False, fp32_out=True, planes_out=True)
     Wp = _PermuteWeight.apply(W).reshape(Ci, k * k * Co)
     if ln is None:
         return _ConvT2dS2.apply(x, Wp, b, k, None, None, 0.0, out_nchw)
-    return _ConvT2dS2.apply(x, Wp, b, k, ln[0], ln[1], float(ln[2]))
+    return _ConvT2dS2.apply(x, Wp, b, k, ln[0], ln[1], float(ln[2]), False, _ln_code(ln))
 
 
 class _TransposeLast2(Function):
@@ -1979,11 +2013,11 @@ def gru_seq(x, mask, h0, W, gamma, beta):
 
 
 class _DenseLNAct(Function):
-    """y = SiLU(LayerNorm([x1, x2] W^T + b)) as one autograd node (Linear + NormLayer + act,
+    """y = act(LayerNorm([x1, x2] W^T + b)), act SiLU or ELU by its code, as one autograd node (Linear + NormLayer + act,
     agent/dreamer_utils.py:739-747,462-463).  The backward runs the LayerNorm backward once and gets
     dgamma, dbeta AND the Linear's bias gradient from the same pass, then the dgrad / wgrad GEMMs."""
     @staticmethod
-    def forward(ctx, x1, x2, W, b, gamma, beta, eps):
+    def forward(ctx, x1, x2, W, b, gamma, beta, eps, act=1):
         a = _f32(x1).reshape(-1, x1.shape[-1]).contiguous()
         c = _f32(x2).reshape(-1, x2.shape[-1]).contiguous() if x2 is not None else None
         M, K1 = a.shape
@@ -1994,8 +2028,9 @@ class _DenseLNAct(Function):
         ctx.w1 = _dense2_fwd(a, c, W, b, pre)
         y = torch.empty_like(pre)
         mean = torch.empty(M, device=a.device); rstd = torch.empty(M, device=a.device)
-        check(lib().genrl_ln_act_fwd(_p(pre), N, _p(gamma), _p(beta), _p(y), N, _p(mean), _p(rstd), M, N, eps, 1,
+        check(lib().genrl_ln_act_fwd(_p(pre), N, _p(gamma), _p(beta), _p(y), N, _p(mean), _p(rstd), M, N, eps, act,
                                      _stream()), 'ln_act_fwd')
+        ctx.act = act
         ctx.save_for_backward(a, c if c is not None else a.new_empty(0), W, gamma, beta, pre, mean, rstd)
         ctx.has2 = c is not None
         ctx.has_bias = b is not None
@@ -2015,16 +2050,16 @@ class _DenseLNAct(Function):
         need_p = ctx.needs_input_grad[2] or ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
         g0, g1, g2, ws, acc_p, direct = _ln_param_targets(M, N, gamma, beta, ctx.bias, dev, need=need_p)
         check(lib().genrl_ln_act_bwd(_p(dy2), N, _p(pre), N, _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dpre), N,
-                                     _p(g0), _p(g1), _p(g2), _p(ws), M, N, 1, acc_p, _stream()), 'ln_act_bwd')
+                                     _p(g0), _p(g1), _p(g2), _p(ws), M, N, ctx.act, acc_p, _stream()), 'ln_act_bwd')
         d1, d2 = _dense2_dgrad(dpre, W, ctx.w1, K1, K2, ctx.needs_input_grad[0], ctx.has2 and ctx.needs_input_grad[1])
         dW = _dense2_wgrad(dpre, a, c if ctx.has2 else None, W) if ctx.needs_input_grad[2] else None
         if need_p and not direct:
-            return _as(d1, ctx.shapes[0]), _as(d2, ctx.shapes[1]), dW, (g2 if ctx.has_bias else None), g0, g1, None
-        return _as(d1, ctx.shapes[0]), _as(d2, ctx.shapes[1]), dW, None, None, None, None
+            return _as(d1, ctx.shapes[0]), _as(d2, ctx.shapes[1]), dW, (g2 if ctx.has_bias else None), g0, g1, None, None
+        return _as(d1, ctx.shapes[0]), _as(d2, ctx.shapes[1]), dW, None, None, None, None, None
 
 
-def dense_ln_act(x1, x2, W, b, gamma, beta, eps=1e-5):
-    return _DenseLNAct.apply(x1, x2, W, b, gamma, beta, float(eps))
+def dense_ln_act(x1, x2, W, b, gamma, beta, eps=1e-5, act='SiLU'):
+    return _DenseLNAct.apply(x1, x2, W, b, gamma, beta, float(eps), act_layer_code(act))
 
 
 # ------------------------------------------------------------------ RSSM observe scan with the posterior inside the recurrence
@@ -2436,31 +2471,37 @@ def ens_var(preds):
 
 # ------------------------------------------------------------------ the DreamerV2 defaults (csrc/rowact.hip, heads.hip, vecobs.hip): norm-free layers, truncated-normal actor, mse heads
 
-def silu_fwd_raw(x, y, M, N, P=None):
-    """y = x sigmoid(x) over M contiguous rows of N floats (y may be x); P: planes of y"""
-    check(lib().genrl_silu_fwd_h2(_p(x), N, _p(y), N, M, N, *_plane_out(P), _stream()), 'silu_fwd_h2')
+_ROW_ACT = {1: 'silu', 2: 'elu'}          # the stand-alone activation kernels (csrc/rowact.hip) by GENRL_ACT_* code
 
 
-def silu_bwd_raw(dy, x, dx, M, N, P=None):
-    """dx = dy silu'(x) from the saved pre-activation x (dx may be dy); P: planes of dx"""
-    check(lib().genrl_silu_bwd_h2(_p(dy), N, _p(x), N, _p(dx), N, M, N, *_plane_out(P), _stream()), 'silu_bwd_h2')
+def act_fwd_raw(act, x, y, M, N, P=None):
+    """y = act(x) over M contiguous rows of N floats (y may be x), act 1 SiLU / 2 ELU; P: planes of y"""
+    name = _ROW_ACT[act]
+    check(getattr(lib(), f'genrl_{name}_fwd_h2')(_p(x), N, _p(y), N, M, N, *_plane_out(P), _stream()), f'{name}_fwd_h2')
+
+
+def act_bwd_raw(act, dy, x, dx, M, N, P=None):
+    """dx = dy act'(x) from the saved pre-activation x (dx may be dy); P: planes of dx"""
+    name = _ROW_ACT[act]
+    check(getattr(lib(), f'genrl_{name}_bwd_h2')(_p(dy), N, _p(x), N, _p(dx), N, M, N, *_plane_out(P), _stream()), f'{name}_bwd_h2')
 
 
 class _DenseAct(Function):
-    """y = SiLU([x1, x2] W^T): Linear without bias + NormLayer('none') + act (agent/dreamer_utils.py:739-747 with `norm: none`,
+    """y = act([x1, x2] W^T), act SiLU or ELU by its code: Linear without bias + NormLayer('none') + act (agent/dreamer_utils.py:739-747 with `norm: none`,
     conf/defaults/dreamer_v2.yaml) as one autograd node on fp32 operands; the layout of _DenseLNAct without the LayerNorm."""
     @staticmethod
-    def forward(ctx, x1, x2, W):
+    def forward(ctx, x1, x2, W, act=1):
         a = _f32(x1).reshape(-1, x1.shape[-1]).contiguous()
         c = _f32(x2).reshape(-1, x2.shape[-1]).contiguous() if x2 is not None else None
         M, K1 = a.shape
         K2 = c.shape[1] if c is not None else 0
         N, K = W.shape
         assert K == K1 + K2 and N % 4 == 0
+        ctx.act = act
         pre = torch.empty(M, N, device=a.device)
         ctx.w1 = _dense2_fwd(a, c, W, None, pre)
         y = torch.empty_like(pre)
-        silu_fwd_raw(pre, y, M, N)
+        act_fwd_raw(act, pre, y, M, N)
         ctx.save_for_backward(a, c if c is not None else a.new_empty(0), W, pre)
         ctx.has2 = c is not None
         ctx.shapes = (x1.shape, x2.shape if x2 is not None else None)
@@ -2473,14 +2514,14 @@ class _DenseAct(Function):
         K2 = c.shape[1] if ctx.has2 else 0
         N = W.shape[0]
         dpre = torch.empty_like(pre)
-        silu_bwd_raw(_f32(dy).reshape(M, N).contiguous(), pre, dpre, M, N)
+        act_bwd_raw(ctx.act, _f32(dy).reshape(M, N).contiguous(), pre, dpre, M, N)
         d1, d2 = _dense2_dgrad(dpre, W, ctx.w1, K1, K2, ctx.needs_input_grad[0], ctx.has2 and ctx.needs_input_grad[1])
         dW = _dense2_wgrad(dpre, a, c if ctx.has2 else None, W) if ctx.needs_input_grad[2] else None
-        return _as(d1, ctx.shapes[0]), _as(d2, ctx.shapes[1]), dW
+        return _as(d1, ctx.shapes[0]), _as(d2, ctx.shapes[1]), dW, None
 
 
-def dense_act(x1, x2, W):
-    return _DenseAct.apply(x1, x2, W)
+def dense_act(x1, x2, W, act='SiLU'):
+    return _DenseAct.apply(x1, x2, W, act_layer_code(act))
 
 
 class _SqErr(Function):

@@ -72,8 +72,8 @@ CONV1_DIRECT = os.environ.get('GENRL_CONV1_DIRECT', '1') != '0'
 KEEP_COLS = True      # (where the first layer still runs im2col + GEMM) the u8 frames' patch matrix is kept for its weight gradient: one im2col launch less
 
 
-def _ln_fwd(pre2d, gamma, beta, eps, want_planes, want_fp32=True):
-    """channel-LayerNorm + SiLU of the rows; -> (y, mean, rstd, uniform planes of y or None, lazy).  want_fp32 False (an inner layer whose
+def _ln_fwd(pre2d, gamma, beta, eps, want_planes, want_fp32=True, act=1):
+    """channel-LayerNorm + SiLU (act 2: ELU) of the rows; -> (y, mean, rstd, uniform planes of y or None, lazy).  want_fp32 False (an inner layer whose
     consumer gathers from the planes): y is allocated but NOT written when the kernel makes the planes itself -- lazy is then a cell
     [True] and a consumer that does read fp32 values after all fills y from the planes first (_need_fp32)"""
     M, N = pre2d.shape
@@ -84,11 +84,11 @@ def _ln_fwd(pre2d, gamma, beta, eps, want_planes, want_fp32=True):
         P = planes.Planes(M, N, pre2d.device, zero=False)
         if not want_fp32 and LAZY_FP32:
             lazy = [True]
-        check(lib().genrl_ln_act_fwd_h2u(_p(pre2d), N, _p(gamma), _p(beta), None if lazy else _p(y), N, _p(mean), _p(rstd), M, N, eps, 1,
+        check(lib().genrl_ln_act_fwd_h2u(_p(pre2d), N, _p(gamma), _p(beta), None if lazy else _p(y), N, _p(mean), _p(rstd), M, N, eps, act,
                                          P.ptr(), P.ld, P.plane, P.inv_ptr(), _stream()), 'ln_act_fwd_h2u')
         P.uniform = True
     else:
-        check(lib().genrl_ln_act_fwd(_p(pre2d), N, _p(gamma), _p(beta), _p(y), N, _p(mean), _p(rstd), M, N, eps, 1, _stream()),
+        check(lib().genrl_ln_act_fwd(_p(pre2d), N, _p(gamma), _p(beta), _p(y), N, _p(mean), _p(rstd), M, N, eps, act, _stream()),
               'ln_act_fwd')
         if want_planes and N % 4 == 0:
             P = _uniform_split(y)
@@ -105,7 +105,7 @@ def _need_fp32(x, cell, xp):
         cell[0] = False
 
 
-def _ln_bwd(dy2d, pre2d, gamma, beta, mean, rstd, bias, want_planes):
+def _ln_bwd(dy2d, pre2d, gamma, beta, mean, rstd, bias, want_planes, act=1):
     """-> dpre, dgamma, dbeta, dbias (None where accumulated straight into the flat gradient buffers), uniform planes of dpre"""
     M, N = pre2d.shape
     dev = pre2d.device
@@ -116,12 +116,12 @@ def _ln_bwd(dy2d, pre2d, gamma, beta, mean, rstd, bias, want_planes):
         P = planes.Planes(M, N, dev, zero=False)
         amax = torch.empty(2048, device=dev)
         check(lib().genrl_ln_act_bwd_h2u(_p(dy2d), N, _p(pre2d), N, _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dpre), N, _p(g0), _p(g1),
-                                         _p(g2), _p(ws), M, N, 1, acc_p, P.ptr(), P.ld, P.plane, P.inv_ptr(), _p(amax), _stream()),
+                                         _p(g2), _p(ws), M, N, act, acc_p, P.ptr(), P.ld, P.plane, P.inv_ptr(), _p(amax), _stream()),
               'ln_act_bwd_h2u')
         P.uniform = True
     else:
         check(lib().genrl_ln_act_bwd(_p(dy2d), N, _p(pre2d), N, _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dpre), N, _p(g0), _p(g1),
-                                     _p(g2), _p(ws), M, N, 1, acc_p, _stream()), 'ln_act_bwd')
+                                     _p(g2), _p(ws), M, N, act, acc_p, _stream()), 'ln_act_bwd')
         if want_planes and N % 4 == 0:
             P = _uniform_split(dpre)
     return (dpre, None, None, None, P) if direct else (dpre, g0, g1, g2, P)
@@ -261,9 +261,10 @@ class _Conv2dS2P(Function):
     """ops._Conv2dS2 with plane products.  x: f32 NHWC (N,H,W,C) [xp: its uniform planes or None] or u8 NCHW frames;
     Wp (Co, k*k*Ci) = weight permuted to (co, kh, kw, ci); channel-LayerNorm + SiLU fused; returns NHWC with ._planes set."""
     @staticmethod
-    def forward(ctx, x, Wp, b, k, gamma, beta, eps, xp, holder, wsrc=(None,), opts=(None, True, True)):
+    def forward(ctx, x, Wp, b, k, gamma, beta, eps, xp, holder, wsrc=(None,), opts=(None, True, True), act=1):
         ctx.wsrc = wsrc[0]
         ctx.xlazy, fp32_out, planes_out = opts      # (cell of a planes-only input; does anything read this layer's fp32 output / planes?)
+        ctx.act = act                               # (the activation behind the channel-LayerNorm: GENRL_ACT_* code)
         u8 = x.dtype == torch.uint8
         x = x.contiguous()
         if u8:
@@ -294,7 +295,7 @@ class _Conv2dS2P(Function):
                     ctx.cols = cols          # (the frames' patch matrix serves the weight gradient again: 0.15 GB at c2, 0.8 GB at c4, of 288)
         if isinstance(fp32_out, tuple):       # the consumer's description: decided by ITS predicates, not by the layer's position
             fp32_out = not consumer_reads_planes_only(fp32_out, Nimg, Ho, Wo, Co)
-        out, mean, rstd, outp, lazy = _ln_fwd(y, gamma, beta, eps, want_planes=planes_out and M >= min_rows(), want_fp32=fp32_out)
+        out, mean, rstd, outp, lazy = _ln_fwd(y, gamma, beta, eps, want_planes=planes_out and M >= min_rows(), want_fp32=fp32_out, act=ctx.act)
         holder.append(outp); holder.append(lazy)
         ctx.dims = (Nimg, Hi, Wi, C, k, u8)
         ctx.bias = b
@@ -316,7 +317,7 @@ class _Conv2dS2P(Function):
         kr = need_dx and M >= min_rows() and Co >= KR_MIN_K
         # (the LayerNorm backward's planes are uniform-scale whenever it makes them itself: Co <= 256)
         sp_maybe = need_dx and SUBPIXEL and _hl_on() and (k % 2 == 0 or SUBPIXEL_ODD) and Co % 8 == 0 and Co >= 48 and C % 4 == 0
-        dy2, dg, dbe, db, dyp = _ln_bwd(dy.reshape(M, Co).contiguous(), pre, gamma, beta, mean, rstd, ctx.bias, want_planes=tn or kr or sp_maybe)
+        dy2, dg, dbe, db, dyp = _ln_bwd(dy.reshape(M, Co).contiguous(), pre, gamma, beta, mean, rstd, ctx.bias, want_planes=tn or kr or sp_maybe, act=ctx.act)
         dx = dW = None
         if ctx.needs_input_grad[1]:
             dW = torch.empty(Co, K, device=dy.device)
@@ -351,16 +352,17 @@ class _Conv2dS2P(Function):
             else:
                 sgemm(dy2, Co, 1, Wp, 1, K, dcols, K, None, M, K, Co)
             dx = ops._col2im(dcols, None, Nimg, Ho, Wo, C, k, Hi, Wi)
-        return dx, dW, db, None, dg, dbe, None, None, None, None, None
+        return dx, dW, db, None, dg, dbe, None, None, None, None, None, None
 
 
 class _ConvT2dS2P(Function):
     """ops._ConvT2dS2 (with the fused channel-LayerNorm + SiLU) with plane products.  x NHWC (N,Hi,Wi,Ci), xp: planes of its rows
     (uniform or per-row scales) or None; Wp (Ci, k*k*Co) = weight permuted to (ci, kh, kw, co)."""
     @staticmethod
-    def forward(ctx, x, Wp, b, k, gamma, beta, eps, xp, holder, wsrc=(None,), opts=(None, True, True)):
+    def forward(ctx, x, Wp, b, k, gamma, beta, eps, xp, holder, wsrc=(None,), opts=(None, True, True), act=1):
         ctx.wsrc = wsrc[0]
         ctx.xlazy, fp32_out, planes_out = opts
+        ctx.act = act
         if ctx.xlazy is not None and not (x.dtype == torch.float32 and x.is_contiguous()):
             _need_fp32(x, ctx.xlazy, xp)
         x = _f32(x).contiguous()
@@ -388,7 +390,7 @@ class _ConvT2dS2P(Function):
         if isinstance(fp32_out, tuple):
             fp32_out = not consumer_reads_planes_only(fp32_out, Nimg, Ho, Wo, Co)
         out, mean, rstd, outp, lazy = _ln_fwd(y.reshape(-1, Co), gamma, beta, eps, want_planes=planes_out and Nimg * Ho * Wo >= min_rows(),
-                                              want_fp32=fp32_out)
+                                              want_fp32=fp32_out, act=ctx.act)
         holder.append(outp); holder.append(lazy)
         ctx.dims = (Nimg, Hi, Wi, Ci, Co, k)
         ctx.bias = b
@@ -407,7 +409,7 @@ class _ConvT2dS2P(Function):
         tn = gather and xp is not None and M % 64 == 0 and ctx.needs_input_grad[1]
         dgr = gather and ctx.needs_input_grad[0]
         dyv, dg, dbe, db, dyp = _ln_bwd(dy.contiguous().reshape(-1, Co), pre.reshape(-1, Co), gamma, beta, mean, rstd, ctx.bias,
-                                       want_planes=tn or dgr)
+                                       want_planes=tn or dgr, act=ctx.act)
         dyv = dyv.reshape(Nimg, Ho, Wo, Co)
         implicit = ops._implicit_conv(dyv, Co) and Ci % 4 == 0
         dcols = None
@@ -434,7 +436,7 @@ class _ConvT2dS2P(Function):
                 if dcols is None:
                     dcols = ops._im2col(dyv, Nimg, Ho, Wo, Co, k, 0)
                 sgemm(x, 1, Ci, dcols, 1, Nw, dW, Nw, None, Ci, Nw, M)
-        return dx, dW, db, None, dg, dbe, None, None, None, None, None
+        return dx, dW, db, None, dg, dbe, None, None, None, None, None, None
 
 
 def conv2d_s2(x, W, b, ln, fp32_out=True, planes_out=True):
@@ -447,7 +449,7 @@ def conv2d_s2(x, W, b, ln, fp32_out=True, planes_out=True):
     Wp = ops._PermuteWeight.apply(W).reshape(Co, k * k * Ci)
     holder = []
     y = _Conv2dS2P.apply(x, Wp, b, k, ln[0], ln[1], float(ln[2]), getattr(x, '_planes', None), holder, (W,),
-                         (getattr(x, '_lazy', None), fp32_out, planes_out))
+                         (getattr(x, '_lazy', None), fp32_out, planes_out), ops._ln_code(ln))
     y._planes, y._lazy = holder if holder else (None, None)
     return y
 
@@ -457,6 +459,6 @@ def convT2d_s2(x, W, b, ln, fp32_out=True, planes_out=True):
     Wp = ops._PermuteWeight.apply(W).reshape(Ci, k * k * Co)
     holder = []
     y = _ConvT2dS2P.apply(x, Wp, b, k, ln[0], ln[1], float(ln[2]), getattr(x, '_planes', None), holder, (W,),
-                          (getattr(x, '_lazy', None), fp32_out, planes_out))
+                          (getattr(x, '_lazy', None), fp32_out, planes_out), ops._ln_code(ln))
     y._planes, y._lazy = holder if holder else (None, None)
     return y

@@ -20,15 +20,15 @@ from .ops import _p, _f32, _ln_param_targets, _wgrad_target, _bias_grad, sgemm, 
 _stream = ops._stream
 
 
-def _ln_fwd(pre_ptr, gamma, beta, y_ptr, mean_ptr, rstd_ptr, M, N, eps, P, row0):
-    check(lib().genrl_ln_act_fwd_h2(pre_ptr, N, _p(gamma), _p(beta), y_ptr, N, mean_ptr, rstd_ptr, M, N, eps, 1,
+def _ln_fwd(pre_ptr, gamma, beta, y_ptr, mean_ptr, rstd_ptr, M, N, eps, P, row0, act=1):
+    check(lib().genrl_ln_act_fwd_h2(pre_ptr, N, _p(gamma), _p(beta), y_ptr, N, mean_ptr, rstd_ptr, M, N, eps, act,
                                     P.ptr(row0), P.ld, P.plane, P.inv_ptr(row0), _stream()), 'ln_act_fwd_h2')
 
 
 def _ln_bwd(dy_ptr, pre_ptr, gamma, beta, mean_ptr, rstd_ptr, dpre_ptr, M, N, P, row0, g0=None, g1=None, g2=None, ws=None,
-            acc_p=0):
+            acc_p=0, act=1):
     check(lib().genrl_ln_act_bwd_h2(dy_ptr, N, pre_ptr, N, _p(gamma), _p(beta), mean_ptr, rstd_ptr, dpre_ptr, N, _p(g0),
-                                    _p(g1), _p(g2), _p(ws), M, N, 1, acc_p, P.ptr(row0), P.ld, P.plane, P.inv_ptr(row0),
+                                    _p(g1), _p(g2), _p(ws), M, N, act, acc_p, P.ptr(row0), P.ld, P.plane, P.inv_ptr(row0),
                                     _stream()), 'ln_act_bwd_h2')
 
 
@@ -292,10 +292,10 @@ class _RolloutPlanes(Function):
 
 # ---- the dense layer on [x1, x2] with plane operands: its three products, defined once for the nodes below (on fp32 operands: ops._dense2_*)
 
-def _dense_fwd(M, in1, in2, W, b, pre, need_w, ln=None):
-    """pre (M, N) = [x1, x2] W^T (+ b) and, with ln = (gamma, beta, eps, out_p, y, mean, rstd), y / out_p = SiLU(LayerNorm(pre)) (y None: planes
-    only).  in1 / in2: (fp32 rows, Planes | None, first row) of the inputs; fp32 rows of in2 None: one input.  The product runs on planes when
-    every input comes with them -- with the LayerNorm and the SiLU in ONE launch where planes.gemm_ln_ok holds (row statistics exchanged inside one
+def _dense_fwd(M, in1, in2, W, b, pre, need_w, ln=None, act=1):
+    """pre (M, N) = [x1, x2] W^T (+ b) and, with ln = (gamma, beta, eps, out_p, y, mean, rstd), y / out_p = act(LayerNorm(pre)) (y None: planes
+    only; act: the GENRL_ACT_* code, 1 SiLU / 2 ELU).  in1 / in2: (fp32 rows, Planes | None, first row) of the inputs; fp32 rows of in2 None: one input.  The product runs on planes when
+    every input comes with them -- with the LayerNorm and the activation in ONE launch where planes.gemm_ln_ok holds (row statistics exchanged inside one
     XCD's L2: genrl_gemm_h2_ln) -- else on the fp32 rows (ops._dense2_fwd).
     -> the inputs' ((P1, r1), (P2, r2)) for the node to keep, where the weight gradient (need_w: somebody wants it) will really take them
     (genrl_gemm_h2_tn); else None: the fp16 copies would live from forward to backward for nothing"""
@@ -311,14 +311,14 @@ def _dense_fwd(M, in1, in2, W, b, pre, need_w, ln=None):
         seg = dict(a_row0=ra, A1=Pb, B1=planes.weight(W, c0=K1), a1_row0=rb) if two else dict(a_row0=ra)
         if fused:
             gamma, beta, eps, out_p, y, mean, rstd = ln
-            planes.gemm_ln(Pa, w1, pre, b, M, N, gamma, beta, eps, out_p, 0, y=y, mean=mean, rstd=rstd, **seg)
+            planes.gemm_ln(Pa, w1, pre, b, M, N, gamma, beta, eps, out_p, 0, y=y, mean=mean, rstd=rstd, act=act, **seg)
         else:
             planes.gemm(Pa, w1, pre, N, b, M, N, **seg)
     else:
         ops._dense2_fwd(a, c, W, b, pre)
     if ln is not None and not fused:
         gamma, beta, eps, out_p, y, mean, rstd = ln
-        _ln_fwd(_p(pre), gamma, beta, _p(y), _p(mean), _p(rstd), M, N, eps, out_p, 0)
+        _ln_fwd(_p(pre), gamma, beta, _p(y), _p(mean), _p(rstd), M, N, eps, out_p, 0, act)
     keep = on_planes and need_w and planes.tn_ok(M, N, K1, K) and (not two or (K - K1) % 4 == 0) and ra % 4 == 0 and rb % 4 == 0
     return ((Pa, ra), (Pb, rb)) if keep else None
 
@@ -441,15 +441,15 @@ def _input_handles(x1, x2, planes_, both_or_none):
     return (h1 if h1 is not None else (None, 0)), (h2 if h2 is not None else (None, 0))
 
 
-def dense_ln_act(x1, x2, W, b, gamma, beta, eps=1e-5, planes=None):
-    """y = SiLU(LayerNorm([x1, x2] W^T + b)) (ops.dense_ln_act, agent/dreamer_utils.py:739-747) on plane operands: a trunk of one layer.
+def dense_ln_act(x1, x2, W, b, gamma, beta, eps=1e-5, planes=None, act='SiLU'):
+    """y = act(LayerNorm([x1, x2] W^T + b)), act 'SiLU' / 'ELU'  (ops.dense_ln_act, agent/dreamer_utils.py:739-747) on plane operands: a trunk of one layer.
     -> y with y._planes = (planes of y, 0) for the next layer.  planes = ((P1, row0), (P2, row0) | None) of the inputs when the caller has them
     (rollout states); otherwise the inputs' own `_planes` attribute (a previous layer's output) is used."""
-    return dense_ln_trunk(x1, x2, [(W, b, gamma, beta, eps)], planes=planes)
+    return dense_ln_trunk(x1, x2, [(W, b, gamma, beta, eps)], planes=planes, act=act)
 
 
 class _TrunkPlanes(Function):
-    """A chain of layers y = SiLU(LayerNorm([x1, x2] W^T + b)) (ops._DenseLNAct; an MLP trunk: agent/dreamer_utils.py:739-747) with plane
+    """A chain of layers y = act(LayerNorm([x1, x2] W^T + b)), one activation (SiLU or ELU, by its code) for the chain (ops._DenseLNAct; an MLP trunk: agent/dreamer_utils.py:739-747) with plane
     operands as ONE autograd node, the way ActorTapePlanes treats the policy.  Per layer: the forward product runs on planes when the inputs
     come with them, the output's planes are written by the LayerNorm kernel, the backward's dgrad products use the planes its LayerNorm
     backward emits and the transposed weight planes, the weight gradient the kept input planes or the fp32-operand kernels (_dense_fwd /
@@ -460,14 +460,15 @@ class _TrunkPlanes(Function):
     leaves the node: the caller gets the last layer's fp32 output alone.  params: (W, b, gamma, beta) per layer; out_ps: the output planes
     per layer; P1 / P2 (+ first rows): the planes of layer 0's inputs, or None."""
     @staticmethod
-    def forward(ctx, x1, x2, P1, r1, P2, r2, eps, out_ps, *params):
+    def forward(ctx, x1, x2, P1, r1, P2, r2, eps, act, out_ps, *params):
+        ctx.act = act
         a = _f32(x1).reshape(-1, x1.shape[-1]).contiguous()
         c = _f32(x2).reshape(-1, x2.shape[-1]).contiguous() if x2 is not None else None
         M, K1 = a.shape
         K2 = c.shape[1] if c is not None else 0
         L = len(out_ps)
         dev = a.device
-        needs_w = [ctx.needs_input_grad[8 + 4 * l] for l in range(L)]
+        needs_w = [ctx.needs_input_grad[9 + 4 * l] for l in range(L)]
         pres, means, rstds, ys, in_planes = [], [], [], [], []
         for l in range(L):
             W, b, gamma, beta = params[4 * l:4 * l + 4]
@@ -483,7 +484,7 @@ class _TrunkPlanes(Function):
             pre = torch.empty(M, N, device=dev)
             y = torch.empty(M, N, device=dev) if keep_y else None
             mean = torch.empty(M, device=dev); rstd = torch.empty(M, device=dev)
-            in_planes.append(_dense_fwd(M, in1, in2, W, b, pre, needs_w[l], (gamma, beta, eps[l], out_ps[l], y, mean, rstd)))
+            in_planes.append(_dense_fwd(M, in1, in2, W, b, pre, needs_w[l], (gamma, beta, eps[l], out_ps[l], y, mean, rstd), ctx.act))
             pres.append(pre); means.append(mean); rstds.append(rstd); ys.append(y)
         ctx.save_for_backward(a, c if c is not None else a.new_empty(0), *params[0::4], *params[2::4], *params[3::4])
         ctx.biases = list(params[1::4])
@@ -502,7 +503,7 @@ class _TrunkPlanes(Function):
         ng = ctx.needs_input_grad
         M, K1_0 = a.shape
         dev = dy.device
-        out = [None] * (8 + 4 * L)
+        out = [None] * (9 + 4 * L)
         dyl = dy.reshape(M, Ws[-1].shape[0]).contiguous()
         for l in range(L - 1, -1, -1):
             W, gamma, beta, b = Ws[l], gammas[l], betas[l], ctx.biases[l]
@@ -510,9 +511,9 @@ class _TrunkPlanes(Function):
             has2 = l == 0 and ctx.has2
             K1 = K1_0 if l == 0 else K
             K2 = K - K1
-            need_w, need_b, need_g = ng[8 + 4 * l], ng[9 + 4 * l], ng[10 + 4 * l]
+            need_w, need_b, need_g = ng[9 + 4 * l], ng[10 + 4 * l], ng[11 + 4 * l]
             # (what the per-layer chain's node sees as its input's requires_grad: anything upstream of this layer that wants a gradient)
-            need_x1 = ng[0] if l == 0 else (ng[0] or ng[1] or any(ng[8:8 + 4 * l]))
+            need_x1 = ng[0] if l == 0 else (ng[0] or ng[1] or any(ng[9:9 + 4 * l]))
             ip = ctx.in_planes[l]
             use_tn = ip is not None and planes.tn_ok(M, N, K1, K) and (not has2 or K2 % 4 == 0)
             planes_only = 256 < N <= 4096 and N % 4 == 0          # (the LayerNorm kernels that write planes themselves)
@@ -520,7 +521,8 @@ class _TrunkPlanes(Function):
             dpre_p = planes.Planes(M, N, dev)
             need_p = need_w or need_b or need_g
             g0, g1, g2, ws, acc_p, direct = _ln_param_targets(M, N, gamma, beta, b, dev, need=need_p)
-            _ln_bwd(_p(dyl), _p(ctx.pres[l]), gamma, beta, _p(ctx.means[l]), _p(ctx.rstds[l]), _p(dpre), M, N, dpre_p, 0, g0, g1, g2, ws, acc_p)
+            _ln_bwd(_p(dyl), _p(ctx.pres[l]), gamma, beta, _p(ctx.means[l]), _p(ctx.rstds[l]), _p(dpre), M, N, dpre_p, 0, g0, g1, g2, ws, acc_p,
+                    ctx.act)
             d1, d2 = _dense_dgrad(dpre_p, W, K1, need_x1, has2 and ng[1])
             dW = None
             if need_w:
@@ -528,9 +530,9 @@ class _TrunkPlanes(Function):
                 assert use_tn or xin is not None, 'the fp32 input of a weight gradient on the fp32-operand kernel was not kept'
                 dW = _dense_wgrad(dpre_p, dpre, ip if use_tn else None, xin, c if has2 else None, W)
             if need_p and not direct:
-                out[8 + 4 * l:12 + 4 * l] = [dW, (g2 if b is not None else None), g0, g1]
+                out[9 + 4 * l:13 + 4 * l] = [dW, (g2 if b is not None else None), g0, g1]
             else:
-                out[8 + 4 * l] = dW
+                out[9 + 4 * l] = dW
             if l == 0:
                 out[0], out[1] = ops._as(d1, ctx.shapes[0]), ops._as(d2, ctx.shapes[1])
             dyl = d1
@@ -539,27 +541,27 @@ class _TrunkPlanes(Function):
         return tuple(out)
 
 
-def dense_ln_trunk(x1, x2, layers, planes=None):
-    """layers: [(W, b, gamma, beta, eps), ...] of a Dense -> LayerNorm -> SiLU chain whose first layer reads [x1, x2] (x2 may be None).
+def dense_ln_trunk(x1, x2, layers, planes=None, act='SiLU'):
+    """layers: [(W, b, gamma, beta, eps), ...] of a Dense -> LayerNorm -> act ('SiLU' / 'ELU') chain whose first layer reads [x1, x2] (x2 may be None).
     -> the last layer's output, with its `_planes` for the head's product; the same values and gradients as dense_ln_act layer by layer
     (see _TrunkPlanes); `planes` as dense_ln_act's"""
     M = x1.numel() // x1.shape[-1]
     (P1, r1), (P2, r2) = _input_handles(x1, x2, planes, True)
     out_ps = [pl.Planes(M, l[0].shape[0], x1.device) for l in layers]
     flat = [q for l in layers for q in l[:4]]
-    y = _TrunkPlanes.apply(x1, x2, P1, r1, P2, r2, [float(l[4]) for l in layers], out_ps, *flat)
+    y = _TrunkPlanes.apply(x1, x2, P1, r1, P2, r2, [float(l[4]) for l in layers], ops.act_layer_code(act), out_ps, *flat)
     y._planes = (out_ps[-1], 0)
     return y
 
 
 class _DenseActPlanes(Function):
-    """ops._DenseAct (y = SiLU([x1, x2] W^T): a norm-free layer of conf/defaults/dreamer_v2.yaml) with plane operands: the product
+    """ops._DenseAct (y = act([x1, x2] W^T), act SiLU or ELU by its code: a norm-free layer of conf/defaults/dreamer_v2.yaml) with plane operands: the product
     runs on the inputs' planes (P1 / P2 with their first rows: a previous layer's output or a rollout's states; inputs that come without
-    are split here), genrl_silu_fwd_h2 writes the output's planes (out_p) for the next product, the backward's genrl_silu_bwd_h2 emits
+    are split here), genrl_silu_fwd_h2 / genrl_elu_fwd_h2 writes the output's planes (out_p) for the next product, the backward's _bwd_h2 emits
     the planes of the pre-activation gradient for the dgrad products (transposed weight planes) and, where planes.tn_ok holds, for the
     weight gradient through genrl_gemm_h2_tn; below that the weight gradient stays on the fp32-operand kernels."""
     @staticmethod
-    def forward(ctx, x1, x2, W, P1, r1, P2, r2, out_p):
+    def forward(ctx, x1, x2, W, P1, r1, P2, r2, out_p, act=1):
         a = _f32(x1).reshape(-1, x1.shape[-1]).contiguous()
         c = _f32(x2).reshape(-1, x2.shape[-1]).contiguous() if x2 is not None else None
         M, K1 = a.shape
@@ -573,7 +575,8 @@ class _DenseActPlanes(Function):
         pre = torch.empty(M, N, device=a.device)
         ctx.in_planes = _dense_fwd(M, (a, P1, r1), (c, P2, r2), W, None, pre, ctx.needs_input_grad[2])
         y = torch.empty_like(pre)
-        ops.silu_fwd_raw(pre, y, M, N, out_p)
+        ops.act_fwd_raw(act, pre, y, M, N, out_p)
+        ctx.act = act
         ctx.save_for_backward(a, c if c is not None else a.new_empty(0), W, pre)
         ctx.has2 = c is not None
         ctx.shapes = (x1.shape, x2.shape if x2 is not None else None)
@@ -586,18 +589,18 @@ class _DenseActPlanes(Function):
         N = W.shape[0]
         dpre = torch.empty_like(pre)
         dpre_p = planes.Planes(M, N, dy.device)
-        ops.silu_bwd_raw(_f32(dy).reshape(M, N).contiguous(), pre, dpre, M, N, dpre_p)
+        ops.act_bwd_raw(ctx.act, _f32(dy).reshape(M, N).contiguous(), pre, dpre, M, N, dpre_p)
         d1, d2 = _dense_dgrad(dpre_p, W, K1, ctx.needs_input_grad[0], ctx.has2 and ctx.needs_input_grad[1])
         dW = _dense_wgrad(dpre_p, dpre, ctx.in_planes, a, c if ctx.has2 else None, W) if ctx.needs_input_grad[2] else None
-        return ops._as(d1, ctx.shapes[0]), ops._as(d2, ctx.shapes[1]), dW, None, None, None, None, None
+        return ops._as(d1, ctx.shapes[0]), ops._as(d2, ctx.shapes[1]), dW, None, None, None, None, None, None
 
 
-def dense_act(x1, x2, W, planes=None):
-    """-> y = SiLU([x1, x2] W^T) with y._planes = (planes of y, 0) for the next layer; `planes` as dense_ln_act's"""
+def dense_act(x1, x2, W, planes=None, act='SiLU'):
+    """-> y = act([x1, x2] W^T), act 'SiLU' / 'ELU', with y._planes = (planes of y, 0) for the next layer; `planes` as dense_ln_act's"""
     M = x1.numel() // x1.shape[-1]
     (P1, r1), (P2, r2) = _input_handles(x1, x2, planes, False)
     out_p = pl.Planes(M, W.shape[0], x1.device)
-    y = _DenseActPlanes.apply(x1, x2, W, P1, r1, P2, r2, out_p)
+    y = _DenseActPlanes.apply(x1, x2, W, P1, r1, P2, r2, out_p, ops.act_layer_code(act))
     y._planes = (out_p, 0)
     return y
 

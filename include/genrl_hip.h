@@ -103,7 +103,7 @@ int genrl_gemm_h2_sample(const uint16_t* a0, long a0_ld, long a0_plane, const fl
                          long b0_plane, const float* b0_inv, int k0, float* C, long ldc, const float* bias, int M, int N,
                          const float* q, long ldq, float unimix, float* sample, long lds, uint16_t* sp, long sld, long splane,
                          float* sinv, void* stream);
-/* Dense -> LayerNorm (-> SiLU) in ONE launch (round 6; replaces genrl_gemm_h2 + genrl_ln_act_fwd_h2 for the MLP / img_step layers of
+/* Dense -> LayerNorm (-> act: GENRL_ACT_*, SiLU or ELU) in ONE launch (round 6; replaces genrl_gemm_h2 + genrl_ln_act_fwd_h2 for the MLP / img_step layers of
  * agent/dreamer_utils.py:718-747, :459-473 at <= 1024 columns): C = A0 B0^T (+ A1 B1^T) + bias as genrl_gemm_h2 (C keeps the pre-activation the
  * LayerNorm backward reads), then y = act(LayerNorm(C) gamma + beta) as fp32 rows (y may be NULL) and as h2 planes with ONE scale for the
  * whole tensor (the bound max|gamma| sqrt(N) + max|beta|; yinv[row] holds the same value in every row), mean / rstd [M].  A LayerNorm row spans
@@ -129,7 +129,7 @@ int genrl_gemm_h2_ln(const uint16_t* a0, long a0_ld, long a0_plane, const float*
 /* UNIFORM-scale h2 planes (one power-of-two scale for the whole tensor, inv[row] the same in every row): what the convolution
  * products need -- a patch row gathers from several pixel rows, a weight gradient sums over them (csrc/gemm_planes*.hip).
  * genrl_split_h2u: from an fp32 matrix, exact tensor maximum (two launches; ws >= 1024 floats).  genrl_ln_act_fwd_h2u: the channel
- * LayerNorm (+SiLU, rows of <= 256 floats, agent/dreamer_utils.py:1031-1040) emits them itself with the scale its parameters
+ * LayerNorm (+SiLU / ELU, rows of <= 256 floats, agent/dreamer_utils.py:1031-1040) emits them itself with the scale its parameters
  * guarantee (|gamma x^ + beta| <= max|gamma| sqrt(N) + max|beta|); y == NULL: planes only (an inner layer's fp32 activation has no reader
  * when the next convolution gathers from the planes forward and backward).  genrl_ln_act_bwd_h2u: its backward leaves one partial maximum
  * of dx per workgroup in amax_ws (>= 2048 floats), a second launch splits dx with the tensor's scale. */
@@ -442,7 +442,15 @@ int genrl_sgemm_skinny_parts(const float* A, long a_rs, const float* B, long b_r
                              long part_stride, int M, int N, int K, int nparts, void* stream);
 
 /* ---- LayerNorm(+SiLU): NormLayer + act (agent/dreamer_utils.py:844-859,462-463,745) and, on NHWC
- * activations, ImgChLayerNorm (:1031-1040).  act: 0 none, 1 SiLU. */
+ * activations, ImgChLayerNorm (:1031-1040).  act: 0 none, 1 SiLU, 2 ELU (torch.nn.ELU, alpha 1: z above 0, expm1(z) below; the `act:`
+ * of a block's configuration, get_act :862-868) -- the GENRL_ACT_* below.  The same codes are taken by genrl_ln_act_{fwd,bwd}, _h2, _h2u and
+ * genrl_gemm_h2_ln, in every instantiation their dispatchers select; any other value returns 1 before a launch.  The plane scales need
+ * no reasoning of their own for ELU: |ELU(z)| <= |z| as |SiLU(z)| <= |z|, so the uniform bound max|gamma| sqrt(N) + max|beta| and the
+ * row-maximum planes hold as they do for SiLU.  The sequence entries (seq.hip), the policy tape, the fused rollout and
+ * genrl_onehot_gather_ln_fwd take no code: they have SiLU built in. */
+#define GENRL_ACT_NONE 0
+#define GENRL_ACT_SILU 1
+#define GENRL_ACT_ELU 2
 int genrl_ln_act_fwd(const float* x, long ldx, const float* gamma, const float* beta, float* y, long ldy, float* mean,
                      float* rstd, int M, int N, float eps, int act, void* stream);
 long genrl_ln_ws_floats(int M, int N);
@@ -651,6 +659,8 @@ int genrl_ens_var_bwd(const float* g, const float* p, long member, long ld, int 
  *   alignment and the optional plane output as genrl_relu_*_h2 above (planes bit-identical to genrl_split_h2 of the fp32 output).
  *   fwd: y = x sigmoid(x) (y may be x).  bwd: dx = dy sigmoid(x) (1 + x (1 - sigmoid(x))) from the saved pre-activation x (dx may be dy).
  *   Large |x| gives no NaN (x = -100: y = -0, dx = -0 dy); a NaN input stays NaN.
+ * genrl_elu_{fwd,bwd}_h2: the same contract for `act: ELU`.  fwd: y = x above 0, expm1(x) below (y may be x).  bwd: dx = dy above 0,
+ *   dy exp(x) below, from the saved pre-activation x (dx may be dy).  x = -100: y = -1, dx = 0; x = 100: y = 100; a NaN input stays NaN.
  * genrl_trunc_normal_head_{fwd,bwd}: DistLayer 'trunc_normal' (:830-834) + TruncatedNormal.sample (tools/utils.py:102-123) on
  *   raw [R, 2A] = [out | std_raw]: mean = tanh(out), std = 2 sigmoid((std_raw + init_std) / 2) + min_std, action = clamp(mean + eps std,
  *   -1 + 1e-6, 1 - 1e-6) (rows ld_action apart, 0 = A).  eps NULL: the mean-only form (action, if given, = clamp(mean)); any of action / mean /
@@ -660,6 +670,10 @@ int genrl_silu_fwd_h2(const float* x, long ldx, float* y, long ldy, int M, int N
                       void* stream);
 int genrl_silu_bwd_h2(const float* dy, long lddy, const float* x, long ldx, float* dx, long lddx, int M, int N, uint16_t* dxp, long ldp,
                       long plane, float* inv, void* stream);
+int genrl_elu_fwd_h2(const float* x, long ldx, float* y, long ldy, int M, int N, uint16_t* yp, long ldp, long plane, float* inv,
+                     void* stream);
+int genrl_elu_bwd_h2(const float* dy, long lddy, const float* x, long ldx, float* dx, long lddx, int M, int N, uint16_t* dxp, long ldp,
+                     long plane, float* inv, void* stream);
 int genrl_trunc_normal_head_fwd(const float* raw, const float* eps, float* action, float* mean, float* std, long R, int A,
                                 float min_std, float init_std, long ld_action, void* stream);
 int genrl_trunc_normal_head_bwd(const float* daction, const float* raw, const float* eps, float* draw, long R, int A, float init_std,
