@@ -33,7 +33,8 @@
 // * up to two (A, B) operand segments per launch (K = K0 + K1): y = [x1, x2] W^T without a concatenation and
 //   without a second read-modify-write pass over C.
 // Tiles: 64x64 (BK 64; wave tile 32x32) for the M ~ 1024 products of the imagination rollout -- 256 tiles, one per CU;
-// 128x128 (wave tile 64x64) from 2048 64-tiles up.  h2: three 32 KiB stages (64x64); 128x128: gemm_planes_hl_kernel below (four
+// 128x128 (wave tile 64x64) from 2048 64-tiles up; 64x192 and 128x64 (wave tiles 32x96, 64x32) where 64x64 tiles would take two or three rounds
+// of the CUs and these take one (h2_route).  h2: three 32 KiB stages (64x64); 128x128: gemm_planes_hl_kernel below (four
 // 32 KiB HALF stages, the h planes and the l planes of a 64-k block alternating; the two-whole-stages instantiation of this kernel
 // stays behind GENRL_PLANES_HL=0); x3: three 48 KiB stages.
 #include "common.h"
@@ -138,18 +139,30 @@ __device__ __forceinline__ void gemm_planes_body(PlaneSeg s0, PlaneSeg s1, float
                                                  const float* __restrict__ bias, int M, int N, int accumulate,
                                                  int tiles_m, int tiles_n, int xcd_m, SampleEpi smp, ConvGather cg, LnEpi ln, PairSel pr) {
   static_assert(!LNE || (TM * TN == 1 && FMT == 1 && !CONV && PF == 0), "LayerNorm epilogue: 64x64 h2 tile");
-  static_assert(!IS_PAIR || (TM * TN == 1 && FMT == 1 && !CONV && PF == 0 && !LNE), "pair of products: 64x64 h2 tile");
+  // RECT: the rectangular h2 tiles of the 1024-row GRU products -- 64 x 192 (TM 1, TN 3) and 128 x 64 (TM 2, TN 1), three class accumulators and
+  // the segment fold as on the 64x64 tile; their DMA pieces are dealt evenly over all four waves (below)
+  constexpr bool RECT = TM != TN;
+  static_assert(!RECT || (FMT == 1 && NACC == 3 && FOLD && !CONV && PF == 0 && !LNE && ((TM == 1 && TN == 3) || (TM == 2 && TN == 1))),
+                "rectangular tiles: 64x192 and 128x64, h2");
+  static_assert(!IS_PAIR || (TN == 1 && (TM == 1 || TM == 2) && FMT == 1 && !CONV && PF == 0 && !LNE), "pair of products: 64x64 or 128x64 h2 tile");
   constexpr int BM = 64 * TM, BN = 64 * TN;
-  static_assert(!(FMT == 1 && FOLD) || (BM == 64 && BN == 64), "segment fold: 64x64 h2 tile");
+  static_assert(!(FMT == 1 && FOLD) || (BM == 64 && BN == 64) || RECT, "segment fold: 64x64, 64x192 and 128x64 h2 tiles");
   constexpr int NPL = FMT ? 2 : 3, NPROD = FMT ? 3 : 6;
   constexpr int ROWB = BK * 2;                         // bytes per tile row per plane
   constexpr int CPR = ROWB / 16;                       // 16-byte chunks per row (8 or 4)
   constexpr int RPC = 1024 / ROWB;                     // tile rows per 1 KiB DMA piece (8 or 16)
-  constexpr int A_BYTES = NPL * BM * ROWB, B_BYTES = NPL * BN * ROWB, STAGE = A_BYTES + B_BYTES;
+  // HP (the 64 x 192 tile): PLANE-ALTERNATING half stages as in gemm_planes_hl_kernel below -- a ring slot holds ONE plane of a 64-k block of A and
+  // B (32 KiB; the h planes, then the l planes), 128-byte row segments, four slots; two h fragment sets and one l set (see the HP K loop)
+  constexpr bool HP = RECT && TN == 3;
+  static_assert(!HP || (BK == 64 && NS == 4), "64 x 192: four half stages of one plane of 64 k");
+  constexpr int NPLS = HP ? 1 : NPL;                   // planes per ring slot
+  constexpr int A_BYTES = NPLS * BM * ROWB, B_BYTES = NPLS * BN * ROWB, STAGE = A_BYTES + B_BYTES;
   constexpr int APIECES = A_BYTES / 1024, BPIECES = B_BYTES / 1024;
   static_assert(APIECES % 2 == 0 && BPIECES % 2 == 0, "pieces split over two waves per operand");
   constexpr int NPA = APIECES / 2, NPB = BPIECES / 2;  // pieces per wave (waves 0,1: A; waves 2,3: B)
-  constexpr int NPMAX = NPA > NPB ? NPA : NPB;
+  static_assert(!RECT || (APIECES + BPIECES) % 4 == 0, "rectangular tiles: the stage's pieces divide over the four waves");
+  // (RECT: wave w carries pieces w NPMAX .. of the stage's A pieces followed by its B pieces -- a wave may carry pieces of both operands)
+  constexpr int NPMAX = RECT ? (APIECES + BPIECES) / 4 : (NPA > NPB ? NPA : NPB);
   constexpr int KS = BK / 16;                          // MFMA k-steps per stage
   // PF > 0 (experiment; no launch uses it): every stage's DMAs are preceded by an L2 PREFETCH of the stage PF further on -- one
   // 4-byte LDS-DMA per 128-byte line (NPF wave-instructions per wave) into a 1 KiB dummy area -- to test whether the K loop waits on
@@ -224,6 +237,8 @@ __device__ __forceinline__ void gemm_planes_body(PlaneSeg s0, PlaneSeg s1, float
   // source of piece i of the next stage = gbase (wave-uniform: operand + k offset, an SGPR pair that advances by one
   // stage) + voff[i] (per lane: plane, tile row, swizzled chunk; constant over the K loop)
   const char* gbase;
+  const char* gbase_b = nullptr;                       // RECT: gbase walks A, gbase_b walks B (a wave's piece picks its operand's)
+  long pl_a = 0, pl_b = 0;                             // HP: plane strides in bytes (h planes -> l planes of a block)
   unsigned voff[NPMAX];
   unsigned pfoff[NPF ? NPF : 1];                       // prefetch: line (plane, tile row) of this lane, k offset 0
   auto setup = [&](const PlaneSeg& s) __attribute__((always_inline)) {
@@ -231,6 +246,22 @@ __device__ __forceinline__ void gemm_planes_body(PlaneSeg s0, PlaneSeg s1, float
     const long ld = isB ? s.b_ld : s.a_ld, plane = isB ? s.b_plane : s.a_plane;
     const int rows_total = isB ? N : M, r0 = isB ? n0 : m0;
     gbase = reinterpret_cast<const char*>(P);
+    if constexpr (RECT) {
+      gbase = reinterpret_cast<const char*>(s.a); gbase_b = reinterpret_cast<const char*>(s.b);
+      pl_a = s.a_plane * 2; pl_b = s.b_plane * 2;
+#pragma unroll
+      for (int i = 0; i < NPMAX; ++i) {
+        const int q = wave * NPMAX + i;                                   // piece of the stage: A's pieces, then B's
+        const bool pb = q >= APIECES;
+        const int qo = pb ? q - APIECES : q, gpo = (pb ? BN : BM) / RPC;
+        const int p = qo / gpo, row = (qo % gpo) * RPC + r_in;
+        const int f = BK == 64 ? (row >> 1) & 7 : (row >> 2) & 3;
+        const long ldo = pb ? s.b_ld : s.a_ld, plo = pb ? s.b_plane : s.a_plane;
+        const int last = (pb ? N : M) - 1, ro = pb ? n0 : m0;
+        voff[i] = (unsigned)((p * plo + (long)min(ro + row, last) * ldo) * 2 + ((slot ^ f) << 4));
+      }
+      return;
+    }
     if constexpr (PF > 0) {
 #pragma unroll
       for (int i = 0; i < NPF; ++i) {
@@ -275,7 +306,7 @@ __device__ __forceinline__ void gemm_planes_body(PlaneSeg s0, PlaneSeg s1, float
       }
     }
   }
-  const unsigned piece0 = lds0 + (isB ? A_BYTES : 0) + (wave & 1) * npieces * 1024;
+  const unsigned piece0 = RECT ? lds0 + wave * NPMAX * 1024 : lds0 + (isB ? A_BYTES : 0) + (wave & 1) * npieces * 1024;
   // ---- fragment side
   const int l32 = lane & 31, h32 = lane >> 5;
   const int f_rd = BK == 64 ? (l32 >> 1) & 7 : (l32 >> 2) & 3;
@@ -356,8 +387,8 @@ __device__ __forceinline__ void gemm_planes_body(PlaneSeg s0, PlaneSeg s1, float
                                        (__attribute__((address_space(3))) void*)(uintptr_t)(lds0 + LN_T), 4, 0, 0);
   }
   const int nk0 = s0.k / BK, nk = nk0 + s1.k / BK;
-  static_assert(NPA == NPB, "square wave grids only (one DMA count per wave)");
-  constexpr int NP = NPA;
+  static_assert(RECT || NPA == NPB, "one DMA count per wave");
+  constexpr int NP = RECT ? NPMAX : NPA;
   if (!(CONV && !isB)) setup(s0);
   int seg_left = nk0, left = nk;      // stages of the current segment / of the product still to be issued
   // Every stage slot is issued unconditionally (one basic block per iteration, uniform vmcnt counts): once the
@@ -392,7 +423,10 @@ __device__ __forceinline__ void gemm_planes_body(PlaneSeg s0, PlaneSeg s1, float
       }
     }
     if (seg_left == 0 && left > 0) { setup(s1); seg_left = left; }       // (at most one switch)
-    else if (!first && left > 0) gbase += BK * 2;
+    else if (!first && left > 0) {
+      gbase += BK * 2;
+      if constexpr (RECT) gbase_b += BK * 2;
+    }
     first = false;
     --seg_left; --left;
   };
@@ -409,21 +443,54 @@ __device__ __forceinline__ void gemm_planes_body(PlaneSeg s0, PlaneSeg s1, float
     if constexpr (CONV) {
       if (!isB) { glds16(gbase + (size_t)(voff[i] + koff[i & 1]), piece0 + buf * STAGE + i * 1024); return; }
     }
+    if constexpr (RECT) {
+      glds16((wave * NPMAX + i >= APIECES ? gbase_b : gbase) + (size_t)voff[i], piece0 + buf * STAGE + i * 1024);      // (wave-uniform choice)
+      return;
+    }
     glds16(gbase + (size_t)voff[i], piece0 + buf * STAGE + i * 1024);
   };
-  // prologue: stages 0 .. NS-1 in flight; stage 0 -> fragment set 0
+  // HP: half-stage bookkeeping (next_half, called before a half stage's DMAs are issued) and fragment reads of ONE plane
+  const int nu0 = 2 * nk0, nu = 2 * nk;                // half stages of segment 0 / of the product
+  int hissued = 0;                                     // half stages booked so far (the pointers stop once all are: later slots re-read the last one)
+  auto next_half = [&]() __attribute__((always_inline)) {
+    if (hissued == nu0 && hissued < nu) setup(s1);     // (at most one switch; -> the h planes of segment 1's first block)
+    else if (hissued > 0 && hissued < nu) {
+      if (hissued & 1) { gbase += pl_a; gbase_b += pl_b; }                     // -> the l planes of the same block
+      else { gbase += 128 - pl_a; gbase_b += 128 - pl_b; }                     // -> the h planes of the next block
+    }
+    ++hissued;
+  };
+  auto read_half = [&](int set, int p, int r, int buf) __attribute__((always_inline)) {      // r-th read (s-major, then block) of the half stage in slot buf
+    const int s = r / NB_, blk = r % NB_;
+    fr[set][s][blk][p] = blk < TM ? ldfrag(a_s[s] + (blk * 32 * ROWB + buf * STAGE)) : ldfrag(b_s[s] + ((blk - TM) * 32 * ROWB + buf * STAGE));
+  };
+  if constexpr (HP) {
 #pragma unroll
-  for (int st = 0; st < NS; ++st) {
-    next_stage();
-    if (st) prefetch();
+    for (int st = 0; st < NS; ++st) {
+      next_half();
 #pragma unroll
-    for (int i = 0; i < NP; ++i) issue_one(st, i);
+      for (int i = 0; i < NP; ++i) issue_one(st, i);
+    }
+    next_half();                         // books half stage NS (issued by half-iteration 0)
+    wait_vm<(NS - 1) * NP>();
+    __builtin_amdgcn_s_barrier();
+#pragma unroll
+    for (int r = 0; r < KS * NB_; ++r) read_half(0, 0, r, 0);
+  } else {
+    // prologue: stages 0 .. NS-1 in flight; stage 0 -> fragment set 0
+#pragma unroll
+    for (int st = 0; st < NS; ++st) {
+      next_stage();
+      if (st) prefetch();
+#pragma unroll
+      for (int i = 0; i < NP; ++i) issue_one(st, i);
+    }
+    next_stage();                        // books stage NS (issued by iteration 0)
+    wait_vm<(NS - 1) * (NP + NPF)>();
+    __builtin_amdgcn_s_barrier();
+#pragma unroll
+    for (int r = 0; r < NR; ++r) read_one(0, r, 0);
   }
-  next_stage();                        // books stage NS (issued by iteration 0)
-  wait_vm<(NS - 1) * (NP + NPF)>();
-  __builtin_amdgcn_s_barrier();
-#pragma unroll
-  for (int r = 0; r < NR; ++r) read_one(0, r, 0);
 
   // h2, two segments: the operands of segment 1 carry other row scales than those of segment 0 -- when the MFMA stream
   // crosses the boundary the accumulators are multiplied by (scale of segment 0) / (scale of segment 1), an exact power of
@@ -438,10 +505,14 @@ __device__ __forceinline__ void gemm_planes_body(PlaneSeg s0, PlaneSeg s1, float
     // a zero row reads global memory
     if (s1.k && wave < 2) {
       typedef __attribute__((address_space(3))) float lds_f32;
-      lds_f32* const f = reinterpret_cast<lds_f32*>((uintptr_t)(lds0 + EPI_AT + 4 * (wave * BM + lane)));
-      if ((wave ? s1.b_inv : s1.a_inv) && zero_row_inv(*f)) {
-        const float* const inv0 = wave ? s0.b_inv : s0.a_inv;
-        *f = inv0 ? inv0[min((wave ? n0 : m0) + lane, (wave ? N : M) - 1)] : 1.f;
+#pragma unroll
+      for (int j = 0; j < (BM > BN ? BM : BN) / 64; ++j) {          // (64 rows / columns per pass: one on the 64x64 tile)
+        if (j >= (wave ? BN : BM) / 64) break;
+        lds_f32* const f = reinterpret_cast<lds_f32*>((uintptr_t)(lds0 + EPI_AT + 4 * (wave * BM + 64 * j + lane)));
+        if ((wave ? s1.b_inv : s1.a_inv) && zero_row_inv(*f)) {
+          const float* const inv0 = wave ? s0.b_inv : s0.a_inv;
+          *f = inv0 ? inv0[min((wave ? n0 : m0) + 64 * j + lane, (wave ? N : M) - 1)] : 1.f;
+        }
       }
     }
   }
@@ -452,21 +523,28 @@ __device__ __forceinline__ void gemm_planes_body(PlaneSeg s0, PlaneSeg s1, float
   int it = 0;                          // stage whose MFMAs are issued next
   auto fold = [&]() __attribute__((always_inline)) {
     if constexpr (FMT == 1) {
+      // (several blocks per wave: the addresses of the segment-0 factors are formed HERE, in this once-taken block -- hoisted out of the K loop, the
+      // 64-bit addresses of 48 column factors stay live next to the accumulators and spill)
+      int Mf = M, Nf = N;
+      if constexpr (TM * TN > 1) asm volatile("" : "+s"(Mf), "+s"(Nf));
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
-        const int row = min(m0 + (wm * TM + i) * 32 + l32, M - 1);
+        const int row = min(m0 + (wm * TM + i) * 32 + l32, Mf - 1);
         const int ri = (wm * TM + i) * 32 + l32;
         const float rf = (s0.a_inv && s1.a_inv) ? pow2_ratio(s0.a_inv[row], epi1(ri)) : (s0.a_inv ? s0.a_inv[row] : (s1.a_inv ? pow2_ratio(1.f, epi1(ri)) : 1.f));
 #pragma unroll
-        for (int j = 0; j < TN; ++j)
+        for (int j = 0; j < TN; ++j) {
+          // (... and one block's 16 column factors in flight at a time)
+          if constexpr (TM * TN > 1) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int v = 0; v < 16; ++v) {
-            const int col = min(n0 + (wn * TN + j) * 32 + 8 * (v / 4) + 4 * h32 + v % 4, N - 1);
+            const int col = min(n0 + (wn * TN + j) * 32 + 8 * (v / 4) + 4 * h32 + v % 4, Nf - 1);
             const int ci = BM + (wn * TN + j) * 32 + 8 * (v / 4) + 4 * h32 + v % 4;
             const float cf = (s0.b_inv && s1.b_inv) ? pow2_ratio(s0.b_inv[col], epi1(ci)) : (s0.b_inv ? s0.b_inv[col] : (s1.b_inv ? pow2_ratio(1.f, epi1(ci)) : 1.f));
 #pragma unroll
             for (int c = 0; c < NACC; ++c) acc[c][i][j][v] *= rf * cf;
           }
+        }
       }
     }
   };
@@ -521,8 +599,74 @@ __device__ __forceinline__ void gemm_planes_body(PlaneSeg s0, PlaneSeg s1, float
       self(self, std::integral_constant<int, p + 1>{}, guarded);
     }
   };
-  while (it + PERIOD <= nk) run(run, std::integral_constant<int, 0>{}, false);
-  run(run, std::integral_constant<int, 0>{}, true);
+  // HP: half-iteration u (u % 4 == U) -- the MFMAs of half stage u from registers: U even (the h planes of block u / 2): h*h -> accumulator 1; U odd
+  // (its l planes; the block's h fragments are still in their set): l*h -> 0, h*l -> 2, per k-step in that order -- every accumulator receives
+  // the products it receives on the 64x64 tile, in k order.  Behind the barrier the reads of half stage u + 1 (slot (U + 1) % 4: the l set, or the
+  // OTHER h set) and the DMAs of half stage u + 4 (slot U, just retired), three or two per MFMA (read, read, DMA).
+  int u = 0;
+  auto half_iter = [&](auto UC) __attribute__((always_inline)) {
+    constexpr int U = decltype(UC)::value;
+    constexpr bool LPH = (U & 1) != 0;
+    constexpr int HS = U >> 1;
+    constexpr int NMH = (LPH ? 2 : 1) * KS * TM * TN, NRH = KS * NB_, NSD = NRH + NP;
+    constexpr int PERH = (NSD + (NMH - KB) - 1) / (NMH - KB);
+    static_assert(U < 0 || (NRH == 2 * NP && PERH <= 3), "side-op pattern: read, read, DMA");
+    auto mfma_h = [&](int m) __attribute__((always_inline)) {
+      const int j = m % TN, i = (m / TN) % TM;
+      if constexpr (!LPH) {
+        const int s = m / (TM * TN);
+        acc[1][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, fr[HS][s][TM + j][0]), __builtin_bit_cast(f16x8_t, fr[HS][s][i][0]),
+                                                              acc[1][i][j], 0, 0, 0);
+      } else {
+        const int s = m / (2 * TM * TN), t = (m / (TM * TN)) % 2;
+        if (t == 0)      // l(A) * h(B)
+          acc[0][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, fr[HS][s][TM + j][0]), __builtin_bit_cast(f16x8_t, fr[0][s][i][1]),
+                                                                acc[0][i][j], 0, 0, 0);
+        else             // h(A) * l(B)
+          acc[2][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, fr[0][s][TM + j][1]), __builtin_bit_cast(f16x8_t, fr[HS][s][i][0]),
+                                                                acc[2][i][j], 0, 0, 0);
+      }
+    };
+    if constexpr (!LPH) {
+      if (u == nu0) fold();            // (wave-uniform; never taken by one-segment products: u < nu == nu0)
+    }
+#pragma unroll
+    for (int m = 0; m < KB; ++m) mfma_h(m);
+    __builtin_amdgcn_sched_barrier(0);
+    wait_vm<(NS - 2) * NP>();          // half stage u + 1 landed (own DMAs); all fragment reads of half stage u have returned
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int m = KB; m < NMH; ++m) {
+      mfma_h(m);
+#pragma unroll
+      for (int o = (m - KB) * PERH; o < (m - KB + 1) * PERH; ++o) {
+        if (o >= NSD) continue;
+        if (o % 3 == 2) issue_one(U, o / 3);
+        else if constexpr (LPH) read_half(1 - HS, 0, o - o / 3, (U + 1) % NS);      // h planes of the next block
+        else read_half(0, 1, o - o / 3, (U + 1) % NS);                               // l planes of this block
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    next_half();
+    ++u;
+  };
+  if constexpr (HP) {
+    while (u + 4 <= nu) {
+      half_iter(std::integral_constant<int, 0>{});
+      half_iter(std::integral_constant<int, 1>{});
+      half_iter(std::integral_constant<int, 2>{});
+      half_iter(std::integral_constant<int, 3>{});
+    }
+    if (u < nu) {                        // (nu is even: one more block)
+      half_iter(std::integral_constant<int, 0>{});
+      half_iter(std::integral_constant<int, 1>{});
+    }
+  } else {
+    while (it + PERIOD <= nk) run(run, std::integral_constant<int, 0>{}, false);
+    run(run, std::integral_constant<int, 0>{}, true);
+  }
   // (the ring's last slots were issued as re-reads of the final stage into buffers nobody reads: they are drained at the very END of
   // the kernel -- no DMA may be in flight into this workgroup's LDS when it exits -- so that their round trip runs under the epilogue;
   // the epilogue's own LDS words sit outside the ring and were covered by the first barrier.  -0.1 to -0.2 us per launch)
@@ -1783,14 +1927,34 @@ int genrl_split_h2_batch(const genrl_split_desc* d, int n, void* stream) {
 // (GENRL_PLANES_2PER=0 / 1: never / always -- experiments).  Measured (scripts/two_per_cu.py, profiles/r05_two_per_cu.txt): 400 tiles
 // 14.0 -> 11.2 us (K 512), 26.9 -> 23.9 (K 1536); 800 tiles 25.8 -> 20.2; 1200 tiles K 1024 58 -> 53; but 256 tiles 11.2 -> 13.8 and 768 tiles
 // at K 2048 62 -> 64 (the two-stage ring is too shallow for long K loops on its own): from 257 tiles up while K <= 1536
-struct H2Route { bool big, two; };
-static H2Route h2_route(int M, int N, int K, bool sample) {
+//
+// rect: a rectangular tile (3: 64 x 192, 4: 128 x 64 -- the genrl_planes_force_tile codes) for a product that would otherwise take MORE than one
+// round of the 256 CUs on the three-stage 64x64 ring (!big, !two, more than 256 tiles: K > 1536 by default) and that one of the two tiles covers in
+// ONE round of at least 7/8 of the CUs (225 .. 256 workgroups): the rollout's GRU forward 1024 x 3072, K = 2048 (768 tiles of 64x64 -> 256 of
+// 64x192) and the pair of its dgrads 1024 x (1024 + 1024), K = 3072 (512 -> 256 of 128x64; `pair`: N = N0 + N1, the column tile stays 64 wide).
+// The same MFMA sequence per element (bit-identical results), 1/3 and 1/4 fewer operand bytes through L2 -> LDS and through the LDS fragment reads.
+// GENRL_PLANES_RECT=0: never; =3 / =4: that tile alone (A/B runs).  Measured: DESIGN.md 4j, profiles/rect_tiles_ab.txt
+struct H2Route { bool big, two; int rect; };
+static int rect_env() {      // 0: off, 3 / 4: one tile only, -1: both
+  static const int v = [] { const char* e = getenv("GENRL_PLANES_RECT"); return !e ? -1 : (e[0] == '0' ? 0 : (e[0] == '3' ? 3 : (e[0] == '4' ? 4 : -1))); }();
+  return v;
+}
+static H2Route h2_route(int M, int N, int K, bool sample, bool pair = false) {
   static const char* two_env = getenv("GENRL_PLANES_2PER");
   const long t64 = (long)cdiv(M, 64) * cdiv(N, 64);
   H2Route r;
   r.big = sample ? false : (g_planes_force_tile ? g_planes_force_tile == 2 : t64 >= 2048);
   r.two = !sample && (two_env ? two_env[0] == '1' : (t64 > 256 && K <= 1536));
-  return r;
+  r.rect = 0;
+  if (sample) return r;
+  if (g_planes_force_tile) {
+    if (g_planes_force_tile == 4 || (g_planes_force_tile == 3 && !pair)) r.rect = g_planes_force_tile;
+  } else if (!r.big && !r.two && t64 > 256 && rect_env() != 0) {
+    const long c192 = (long)cdiv(M, 64) * cdiv(N, 192), c128 = (long)cdiv(M, 128) * cdiv(N, 64);
+    if (!pair && rect_env() != 4 && c192 > 224 && c192 <= 256) r.rect = 3;
+    else if (rect_env() != 3 && c128 > 224 && c128 <= 256) r.rect = 4;
+  }
+  return r;      // (a forced rectangular tile goes before `two`)
 }
 
 /* The same product on h2 operands: C[m,n] = sum_seg ainv_seg[m] binv_seg[n] sum_k (h_a h_b + (h_a l_b + l_a h_b) / 2^11) */
@@ -1802,7 +1966,8 @@ static int gemm_h2_impl(const uint16_t* a0, long a0_ld, long a0_plane, const flo
   if (M <= 0 || N <= 0 || k0 <= 0 || (k0 & 63) || (k1 & 63) || k1 < 0) return GENRL_EINVAL;
   if ((a0_ld & 7) || (b0_ld & 7) || (k1 && ((a1_ld & 7) || (b1_ld & 7)))) return GENRL_EINVAL;
   PlaneSeg s0{a0, a0_ld, a0_plane, b0, b0_ld, b0_plane, k0, a0_inv, b0_inv}, s1{a1, a1_ld, a1_plane, b1, b1_ld, b1_plane, k1, a1_inv, b1_inv};
-  // (128x128 tiles for the 1024x3072 GRU products -- 192 tiles -- measured neutral in the step: 29.65 vs 29.72 ms)
+  // (128x128 tiles for the 1024x3072 GRU products -- 192 tiles -- measured neutral in the step: 29.65 vs 29.72 ms; 64x192 tiles -- 256, one per CU
+  // in one round: h2_route's `rect` -- 58 -> 49.8 us per launch, and the pair of their dgrads on 128x64 tiles 50.7 -> 45.7 us: 20.90 -> 20.72 ms)
   const H2Route rt = h2_route(M, N, k0 + k1, smp.q != nullptr);
   const bool big = rt.big;
   if (big && !g_planes_force_tile) {
@@ -1845,6 +2010,22 @@ static int gemm_h2_impl(const uint16_t* a0, long a0_ld, long a0_plane, const flo
                                                                                            xcd_split(tm, tn), SampleEpi{}, ConvGather{}, LnEpi{});
       GENRL_CHECK_LAUNCH();
     }
+  } else if (rt.rect) {
+    // one workgroup per CU in ONE round (h2_route).  128 x 64: three 48 KiB stages of 64 k.  64 x 192: a 64-k stage is 64 KiB, three do not fit --
+    // four plane-alternating half stages of 32 KiB (HP in the body; 128-byte row segments, three slots in flight behind the one in use).  Tried
+    // first and measured: four half stages of BK = 32 (64-byte row segments, both planes) -- 59.9 us per 1024 x 3072 x 2048 launch against
+    // 62 on 64x64 tiles, next to nothing for 1/3 fewer bytes: every 128-byte line is requested twice; plane-alternating: 49.8 us.  Two whole 64 KiB stages
+    // spill (261 VGPRs).  profiles/rect_tiles_ab.txt
+    const bool w = rt.rect == 3;
+    const int tm = cdiv(M, w ? 64 : 128), tn = cdiv(N, w ? 192 : 64);
+    log_launch("h2/rect", M, N, k0 + k1, kk_bytes(M, N, k0 + k1));
+    route(w ? GENRL_ROUTE_64X192 : GENRL_ROUTE_128X64);
+    if (w)
+      gemm_planes_kernel<1, 3, 64, 3, 1, 4, true><<<tm * tn, 256, 0, (hipStream_t)stream>>>(s0, s1, C, ldc, bias, M, N, accumulate, tm, tn, xcd_split(tm, tn),
+                                                                                          SampleEpi{}, ConvGather{}, LnEpi{});
+    else
+      gemm_planes_kernel<2, 1, 64, 3, 1, 3, true><<<tm * tn, 256, 0, (hipStream_t)stream>>>(s0, s1, C, ldc, bias, M, N, accumulate, tm, tn, xcd_split(tm, tn),
+                                                                                          SampleEpi{}, ConvGather{}, LnEpi{});
   } else {
     const int tm = cdiv(M, 64), tn = cdiv(N, 64);
     // three 32 KiB stages (96 KiB): a fourth stage measured +0.6 ms on the whole step (28.86 vs 28.2 ms) -- with 128 KiB
@@ -1951,7 +2132,8 @@ int genrl_gemm_h2(const uint16_t* a0, long a0_ld, long a0_plane, const float* a0
 /* Two products on ONE A operand in one launch: C0 (+)= A B0^T (M x N0) and C1 (+)= A B1^T (M x N1), one segment of k columns each, no bias
  * (a backward's two dgrads of one gradient: the GRU's d h and d x).  Column tile t < N0 / 64 of the launch belongs to product 0, the rest to
  * product 1; every tile runs genrl_gemm_h2's 64x64 tile body (three-stage ring) on its own product's (B, C, ldc, accumulate), so each C
- * is bitwise what its own genrl_gemm_h2 launch gives.  GENRL_EINVAL -- the caller launches the two products itself -- unless N0 % 64 == 0
+ * is bitwise what its own genrl_gemm_h2 launch gives (also where the launch as a whole runs on 128x64 tiles, h2_route: the same MFMA sequence per
+ * element).  GENRL_EINVAL -- the caller launches the two products itself -- unless N0 % 64 == 0
  * and genrl_gemm_h2 would run BOTH products on that instantiation (fewer than 2048 64-tiles each, and not the two-stage ring of 257+ tiles
  * with k <= 1536). */
 int genrl_gemm_h2_pair(const uint16_t* a, long a_ld, long a_plane, const float* a_inv, int k,
@@ -1962,18 +2144,23 @@ int genrl_gemm_h2_pair(const uint16_t* a, long a_ld, long a_plane, const float* 
   route_reset();
   if (M <= 0 || N0 <= 0 || N1 <= 0 || k <= 0 || (k & 63) || (N0 & 63) || !a || !b0 || !b1 || !C0 || !C1) return GENRL_EINVAL;
   if ((a_ld & 7) || (b0_ld & 7) || (b1_ld & 7)) return GENRL_EINVAL;
-  const int tm = cdiv(M, 64), tn0 = N0 / 64, tn1 = cdiv(N1, 64), tn = tn0 + tn1;
+  int tm = cdiv(M, 64);
+  const int tn0 = N0 / 64, tn1 = cdiv(N1, 64), tn = tn0 + tn1;
   for (int i = 0; i < 2; ++i) {          // the route genrl_gemm_h2 takes for each product alone
     const H2Route rt = h2_route(M, i ? N1 : N0, k, false);
     if (rt.big || rt.two) return GENRL_EINVAL;
   }
   const PlaneSeg s0{a, a_ld, a_plane, b0, b0_ld, b0_plane, k, a_inv, b0_inv};
+  // the launch as a whole on 128 x 64 tiles where they cover it in one round (h2_route; the column tile stays 64 wide: the same tile -> product map)
+  const bool rect = (long)N0 + N1 <= 0x7fffffffL && h2_route(M, N0 + N1, k, false, true).rect == 4;
+  if (rect) tm = cdiv(M, 128);
   const int xm = xcd_split(tm, tn);
   const int nx = xm > 0 ? 8 / xm : 0;
   const PairSel pr{b1, b1_ld, b1_plane, b1_inv, C1, ldc1, N1, accumulate1, tn0, (nx > 0 && tn0 % nx == 0 && tn1 % nx == 0) ? nx : 0};
-  log_launch("h2/64", M, (long)N0 + N1, k, kk_bytes(M, (long)N0 + N1, k));
-  route(GENRL_ROUTE_64_NS3);
-  gemm_planes_kernel<1, 1, 64, 3, 1, 3, PairOfProducts><<<tm * tn, 256, 0, (hipStream_t)stream>>>(s0, C0, ldc0, M, N0, accumulate0, tm, tn, xm, pr);
+  log_launch(rect ? "h2/rect" : "h2/64", M, (long)N0 + N1, k, kk_bytes(M, (long)N0 + N1, k));
+  route(rect ? GENRL_ROUTE_128X64 : GENRL_ROUTE_64_NS3);
+  if (rect) gemm_planes_kernel<2, 1, 64, 3, 1, 3, PairOfProducts><<<tm * tn, 256, 0, (hipStream_t)stream>>>(s0, C0, ldc0, M, N0, accumulate0, tm, tn, xm, pr);
+  else gemm_planes_kernel<1, 1, 64, 3, 1, 3, PairOfProducts><<<tm * tn, 256, 0, (hipStream_t)stream>>>(s0, C0, ldc0, M, N0, accumulate0, tm, tn, xm, pr);
   GENRL_CHECK_LAUNCH();
   return GENRL_OK;
 }

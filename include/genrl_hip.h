@@ -89,7 +89,8 @@ int genrl_gemm_h2(const uint16_t* a0, long a0_ld, long a0_plane, const float* a0
  * each tile runs genrl_gemm_h2's 64x64 tile body on its own product's (B, C, ldc, accumulate): each C is bitwise what its own genrl_gemm_h2
  * launch gives.  The tile order places both products' tiles of a row panel on the same XCDs, so that A is fetched once per XCD.
  * GENRL_EINVAL -- the caller launches the two products itself -- unless N0 % 64 == 0 and genrl_gemm_h2 would run both products on the
- * three-stage 64x64 instantiation (fewer than 2048 tiles each; not 257+ tiles with k <= 1536). */
+ * three-stage 64x64 instantiation (fewer than 2048 tiles each; not 257+ tiles with k <= 1536).  A launch of more than 256 such tiles that
+ * 128x64 tiles cover in 225 .. 256 workgroups runs on those (the same tile -> product map and the same bits; GENRL_PLANES_RECT=0: never). */
 int genrl_gemm_h2_pair(const uint16_t* a, long a_ld, long a_plane, const float* a_inv, int k,
                        const uint16_t* b0, long b0_ld, long b0_plane, const float* b0_inv, float* C0, long ldc0, int N0, int accumulate0,
                        const uint16_t* b1, long b1_ld, long b1_plane, const float* b1_inv, float* C1, long ldc1, int N1, int accumulate1,
@@ -366,7 +367,7 @@ int genrl_split_x3(const float* x, long ldx, int R, int Cn, uint16_t* out, long 
 int genrl_gemm_x3(const uint16_t* a0, long a0_ld, long a0_plane, const uint16_t* b0, long b0_ld, long b0_plane, int k0,
                   const uint16_t* a1, long a1_ld, long a1_plane, const uint16_t* b1, long b1_ld, long b1_plane, int k1,
                   float* C, long ldc, const float* bias, int M, int N, int accumulate, void* stream);
-int genrl_planes_force_tile(int t);      /* experiments: 0 auto, 1 64x64 tiles, 2 128x128 tiles (both formats) */
+int genrl_planes_force_tile(int t);      /* experiments: 0 auto, 1 64x64 tiles, 2 128x128 tiles (both formats), 3 64x192, 4 128x64 tiles (h2) */
 /* kernel instantiations the most recent plane product entry call (genrl_gemm_h2, _sample, _ln, _conv, _subpixel, _tn, _tn_conv,
  * genrl_gemm_x3) launched, reset by each such call (a refused call reports none): the GENRL_ROUTE_* bits OR-ed in the low 32 bits
  * -- a row-split product or a two-segment 128-tile product reports both of its launches -- and the split-K count of a TN product
@@ -389,6 +390,8 @@ long genrl_planes_last_route(void);
 #define GENRL_ROUTE_X3_128        0x4000u
 #define GENRL_ROUTE_TN            0x8000u
 #define GENRL_ROUTE_TN_CONV       0x10000u
+#define GENRL_ROUTE_64X192        0x20000u  /* 64x192 tile, four plane-alternating half stages: one round of 225 .. 256 workgroups */
+#define GENRL_ROUTE_128X64        0x40000u  /* 128x64 tile, three-stage ring (also the pair of products): one round of 225 .. 256 workgroups */
 
 /* Row kernels with an additional h2-plane output (the operand of the next genrl_gemm_h2): same arithmetic and fp32
  * outputs as the entry points without the suffix (documented below), plus planes [.][ldp] `plane` elements apart and
