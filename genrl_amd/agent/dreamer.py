@@ -391,7 +391,11 @@ class WorldModel(Module):  # ref :120-321
 
     def preprocess(self, obs):  # ref :289-305; uint8 frames stay uint8 (x/255-0.5 is fused downstream)
         obs = dict(obs)
-        assert self.cfg.clip_rewards == 'identity'
+        clip = self.cfg.clip_rewards           # ref :297-301: the reward head's target, nothing else reads it
+        if clip not in ('identity', 'sign', 'tanh'):
+            raise NotImplementedError(clip)
+        if clip != 'identity' and 'reward' in obs:
+            obs['reward'] = getattr(torch, clip)(obs['reward'])
         obs['discount'] = (1.0 - obs['is_terminal'].float())
         if 'reward' in obs and len(obs['discount'].shape) < len(obs['reward'].shape):
             obs['discount'] = obs['discount'].unsqueeze(-1)

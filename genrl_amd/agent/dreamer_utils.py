@@ -765,8 +765,8 @@ class _CatLatent(_Latent):
     def unif_dist(self, state):
         return OneHotDist(torch.ones_like(state['logit']), site='rssm.unif')
 
-    def kl(self, lhs, rhs, mix, free):        # mix max(KL(l || sg r), free).mean() + (1 - mix) max(KL(sg l || r), free).mean() as one node
-        return ops.kl_balance(lhs['logit'], rhs['logit'], mix, free)
+    def kl(self, lhs, rhs, mix, free, mode='balanced'):   # mix max(KL(l || sg r), free).mean() + (1 - mix) max(KL(sg l || r), free).mean() as one node
+        return ops.kl_balance(lhs['logit'], rhs['logit'], mix, free, mode)
 
 
 class _NormalLatent(_Latent):
@@ -795,8 +795,8 @@ class _NormalLatent(_Latent):
     def unif_dist(self, state):               # N(0, 1), ref :427-429
         return LatentNormalDist(torch.zeros_like(state['mean']), torch.ones_like(state['std']), site='rssm.unif')
 
-    def kl(self, lhs, rhs, mix, free):        # the same node on Normal latents (torch's kl_normal_normal under Independent(., 1))
-        return ops.gauss_kl_balance(lhs['mean'], lhs['std'], rhs['mean'], rhs['std'], mix, free)
+    def kl(self, lhs, rhs, mix, free, mode='balanced'):   # the same node on Normal latents (torch's kl_normal_normal under Independent(., 1))
+        return ops.gauss_kl_balance(lhs['mean'], lhs['std'], rhs['mean'], rhs['std'], mix, free, mode)
 
 
 class EnsembleRSSM(Module):  # ref :302-555
@@ -1021,11 +1021,12 @@ class EnsembleRSSM(Module):  # ref :302-555
 
     # ---- losses
     def kl_loss(self, post, prior, forward, balance, free, free_avg):
-        """ref :534-555 (balance != 0.5, free_avg False)."""
-        assert balance != 0.5 and not free_avg
+        """ref :534-555.  The reference tests `balance == 0.5` first, on the Python float, and reads neither mix nor free_avg in that
+        branch; the loss of its free_avg branch has shape [1], here it stays 0-d."""
         lhs, rhs = (prior, post) if forward else (post, prior)
         mix = balance if forward else (1 - balance)
-        return self._latent.kl(lhs, rhs, mix, free)
+        mode = 'unbalanced' if balance == 0.5 else ('free_avg' if free_avg else 'balanced')
+        return self._latent.kl(lhs, rhs, mix, free, mode)
 
 
 # ----------------------------------------------------------------------------- optimiser

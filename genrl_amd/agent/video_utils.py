@@ -73,6 +73,10 @@ class VideoSSM(common.EnsembleRSSM):
         super().__init__(*args, **kwargs)
         if self._act != 'SiLU':          # (the aligner, the action MLP and the teacher-forced prior below are SiLU layers)
             raise NotImplementedError(f"the connector runs SiLU layers: `connector_rssm.act` is {self._act!r} (DESIGN 5n)")
+        if connector_kl.get('free_avg', False):
+            # the reference's connector raises on it: its free_avg loss has shape [1] and VideoSSM.update adds it in place into a 0-d
+            # tensor (agent/video_utils.py:195), so there is nothing to compare against
+            raise NotImplementedError('`connector_kl.free_avg: True` is refused: the reference\'s connector raises on it (DESIGN 5o)')
         assert not temporal_embeds and token_dropout == 0 and detached_post and learn_initial, \
             'shipped connector configuration only (agent/genrl.yaml:15)'
         hidden, deter, norm, act_dim = kwargs['hidden'], kwargs['deter'], kwargs['norm'], kwargs['action_dim']

@@ -392,6 +392,48 @@ __global__ void kl_balance_bwd_kernel(const float* __restrict__ kl, const float*
   gq[i] = (1.0f - mix) * g;
 }
 
+// ------------------------------------------------------------------ the KL loss in its three modes (GENRL_KL_*)
+// EnsembleRSSM.kl_loss, agent/dreamer_utils.py:534-555, every branch.  BALANCED is the pair above, expression for expression.
+// UNBALANCED (balance == 0.5): loss = mean(max(kl, free)), ONE KL whose gradient reaches both sides, so gp = gq.  FREE_AVG: the
+// clamp acts on the mean, loss = mix * max(mean(kl), free) + (1 - mix) * max(mean(kl), free); every row passes gloss / R while the
+// mean lies above free and nothing below it.  One workgroup, fixed summation order; mean(kl) goes to a device scalar that the
+// backward of FREE_AVG reads, so nothing is decided on the host.
+__global__ __launch_bounds__(256) void kl_loss_fwd_kernel(const float* __restrict__ kl, long R, int mode, float mix, float free_,
+                                                         float* __restrict__ loss, float* __restrict__ mean) {
+  __shared__ float red[8];
+  float a = 0.f, s = 0.f;
+  for (long i = threadIdx.x; i < R; i += 256) {
+    const float v = kl[i];
+    a += fmaxf(v, free_);
+    s += v;
+  }
+  a = block_sum_256(a, red);
+  s = block_sum_256(s, red);
+  if (threadIdx.x == 0) {
+    const float ms = s / (float)R;
+    if (mean) *mean = ms;
+    const float m = mode == GENRL_KL_FREE_AVG ? fmaxf(ms, free_) : a / (float)R;
+    *loss = mode == GENRL_KL_UNBALANCED ? m : mix * m + (1.0f - mix) * m;
+  }
+}
+// torch.maximum's gradient: all of it above free, half at a tie, none below -- per row, or on the mean in FREE_AVG.  Every element
+// of gp and gq is written, the zeros included.
+__global__ void kl_loss_bwd_kernel(const float* __restrict__ kl, const float* __restrict__ mean, const float* __restrict__ gloss,
+                                   long R, int mode, float mix, float free_, float* __restrict__ gp, float* __restrict__ gq) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= R) return;
+  const float gm = gloss[0] / (float)R;
+  const float v = mode == GENRL_KL_FREE_AVG ? mean[0] : kl[i];
+  const float g = v > free_ ? gm : (v == free_ ? 0.5f * gm : 0.f);
+  if (mode == GENRL_KL_UNBALANCED) {
+    gp[i] = g;
+    gq[i] = g;
+  } else {
+    gp[i] = mix * g;
+    gq[i] = (1.0f - mix) * g;
+  }
+}
+
 // ------------------------------------------------------------------ lambda-return scan
 // R_t = r_t + g_t*((1-lam)*v_{t+1} + lam*R_{t+1}), R_H = v_H.  reward [H,N], value [H+1,N].
 // ref: lambda_return, agent/dreamer_utils.py:228-253.  One thread per column; coalesced over N.
@@ -757,6 +799,29 @@ int genrl_kl_balance_bwd(const float* kl, const float* gloss, long R, float mix,
   GENRL_ENTER();
   if (R <= 0) return GENRL_OK;
   hipLaunchKernelGGL(kl_balance_bwd_kernel, dim3(cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream, kl, gloss, R, mix,
+                     free_nats, gp, gq);
+  GENRL_CHECK_LAUNCH();
+  return GENRL_OK;
+}
+
+static inline bool bad_kl_mode(int mode) {
+  return mode != GENRL_KL_BALANCED && mode != GENRL_KL_UNBALANCED && mode != GENRL_KL_FREE_AVG;
+}
+
+int genrl_kl_loss_fwd(const float* kl, long R, int mode, float mix, float free_nats, float* loss, float* mean, void* stream) {
+  GENRL_ENTER();
+  if (R < 1 || bad_kl_mode(mode) || !kl || !loss || (mode == GENRL_KL_FREE_AVG && !mean)) return GENRL_EINVAL;
+  hipLaunchKernelGGL(kl_loss_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, kl, R, mode, mix, free_nats, loss, mean);
+  GENRL_CHECK_LAUNCH();
+  return GENRL_OK;
+}
+
+int genrl_kl_loss_bwd(const float* kl, const float* mean, const float* gloss, long R, int mode, float mix, float free_nats,
+                      float* gp, float* gq, void* stream) {
+  GENRL_ENTER();
+  if (R < 1 || bad_kl_mode(mode) || !gloss || !gp || !gq) return GENRL_EINVAL;
+  if (mode == GENRL_KL_FREE_AVG ? !mean : !kl) return GENRL_EINVAL;
+  hipLaunchKernelGGL(kl_loss_bwd_kernel, dim3(cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream, kl, mean, gloss, R, mode, mix,
                      free_nats, gp, gq);
   GENRL_CHECK_LAUNCH();
   return GENRL_OK;

@@ -542,13 +542,35 @@ def _time_major(x):
     return x.contiguous(), False
 
 
+# the branch of EnsembleRSSM.kl_loss (agent/dreamer_utils.py:542-554) a `kl:` / `connector_kl:` block selects -> its GENRL_KL_* code in the
+# C entries: 'unbalanced' is `balance: 0.5` (one KL, gradient into both sides), 'free_avg' clamps the mean instead of the rows
+KL_MODES = {'balanced': 0, 'unbalanced': 1, 'free_avg': 2}
+
+
+def _kl_loss_fwd(kl, R, mode, mix, free):
+    """per-row KL -> (0-d loss, mean(kl) as a device scalar for the backward of 'free_avg', else None)"""
+    loss = torch.empty((), device=kl.device)
+    mean = torch.empty((), device=kl.device) if mode == KL_MODES['free_avg'] else None
+    check(lib().genrl_kl_loss_fwd(_p(kl), R, mode, mix, free, _p(loss), _p(mean), _stream()), 'kl_loss_fwd')
+    return loss, mean
+
+
+def _kl_loss_bwd(kl, mean, gloss, mode, mix, free):
+    """-> gp, gq: the per-row upstream gradients of the KL's left and right side"""
+    R = kl.numel()
+    gp = torch.empty(R, device=kl.device); gq = torch.empty(R, device=kl.device)
+    check(lib().genrl_kl_loss_bwd(_p(kl), _p(mean), _p(gloss.contiguous()), R, mode, mix, free, _p(gp), _p(gq), _stream()),
+          'kl_loss_bwd')
+    return gp, gq
+
+
 class _KLBalance(Function):
-    """EnsembleRSSM.kl_loss's arithmetic as one node (agent/dreamer_utils.py:534-555, balance != 0.5, free_avg False):
+    """EnsembleRSSM.kl_loss's arithmetic as one node (agent/dreamer_utils.py:534-555; mode 'balanced', the others: KL_MODES):
     loss = mix * mean(max(KL(l || sg r), free)) + (1 - mix) * mean(max(KL(sg l || r), free)), plus the per-row KL.
     Forward: the KL kernel + a one-workgroup clamp-mean; backward: the per-row upstream gradients of both sides
     and ONE KL-backward launch (gp scales dl, gq scales dr) -- the elementwise formulation was ~25 launches."""
     @staticmethod
-    def forward(ctx, l, r, mix, free):
+    def forward(ctx, l, r, mix, free, mode):
         ctx.set_materialize_grads(False)         # (no zero tensor for the metric output's absent gradient)
         l, tl = _time_major(_f32(l)); r, tr = _time_major(_f32(r))
         if tl != tr:
@@ -559,10 +581,9 @@ class _KLBalance(Function):
         R = l.numel() // (S * K)
         kl = torch.empty(R, device=l.device)
         check(lib().genrl_cat_kl_fwd(_p(l), _p(r), _p(kl), None, None, R, S, K, UNIMIX, _stream()), 'cat_kl_fwd')
-        loss = torch.empty((), device=l.device)
-        check(lib().genrl_kl_balance_fwd(_p(kl), R, mix, free, _p(loss), _stream()), 'kl_balance_fwd')
-        ctx.save_for_backward(l, r, kl)
-        ctx.mix, ctx.free = mix, free
+        loss, mean = _kl_loss_fwd(kl, R, mode, mix, free)
+        ctx.save_for_backward(l, r, kl, mean)
+        ctx.mix, ctx.free, ctx.mode = mix, free, mode
         value = kl.reshape(l.shape[:-2])
         if tl:
             value = value.transpose(0, 1)
@@ -571,24 +592,22 @@ class _KLBalance(Function):
 
     @staticmethod
     def backward(ctx, gloss, _gvalue):
-        l, r, kl = ctx.saved_tensors
+        l, r, kl, mean = ctx.saved_tensors
         S, K = l.shape[-2:]
         R = kl.numel()
-        gp = torch.empty(R, device=l.device); gq = torch.empty(R, device=l.device)
-        check(lib().genrl_kl_balance_bwd(_p(kl), _p(gloss.contiguous()), R, ctx.mix, ctx.free, _p(gp), _p(gq), _stream()),
-              'kl_balance_bwd')
+        gp, gq = _kl_loss_bwd(kl, mean, gloss, ctx.mode, ctx.mix, ctx.free)
         dl = torch.empty_like(l) if ctx.needs_input_grad[0] else None
         dr = torch.empty_like(r) if ctx.needs_input_grad[1] else None
         check(lib().genrl_cat_kl_bwd(_p(l), _p(r), _p(gp), _p(gq), _p(dl), _p(dr), R, S, K, UNIMIX, _stream()), 'cat_kl_bwd')
         if ctx.tm:
             dl = dl.transpose(0, 1) if dl is not None else None
             dr = dr.transpose(0, 1) if dr is not None else None
-        return dl, dr, None, None
+        return dl, dr, None, None, None
 
 
-def kl_balance(l, r, mix, free):
-    """-> (scalar loss, per-row KL value [detached])"""
-    return _KLBalance.apply(l, r, float(mix), float(free))
+def kl_balance(l, r, mix, free, mode='balanced'):
+    """-> (scalar loss, per-row KL value [detached]); mode: a name of KL_MODES"""
+    return _KLBalance.apply(l, r, float(mix), float(free), KL_MODES[mode])
 
 
 def cat_entropy(logits):
@@ -2611,10 +2630,10 @@ def _same_order(ts):
 
 
 class _GaussKLBalance(Function):
-    """_KLBalance for Normal latents: the Normal-Normal KL kernel, then genrl_kl_balance_fwd; backward: genrl_kl_balance_bwd's two per-row
+    """_KLBalance for Normal latents: the Normal-Normal KL kernel, then genrl_kl_loss_fwd; backward: genrl_kl_loss_bwd's two per-row
     vectors and ONE genrl_gauss_kl_bwd launch (gp scales the left side's gradients, gq the right side's)."""
     @staticmethod
-    def forward(ctx, lm, ls, rm, rs, mix, free):
+    def forward(ctx, lm, ls, rm, rs, mix, free, mode):
         ctx.set_materialize_grads(False)
         (lm, ls, rm, rs), tm = _same_order([lm, ls, rm, rs])
         assert lm.shape == ls.shape == rm.shape == rs.shape, (lm.shape, ls.shape, rm.shape, rs.shape)
@@ -2623,10 +2642,9 @@ class _GaussKLBalance(Function):
         R = lm.numel() // S
         kl = torch.empty(R, device=lm.device)
         check(lib().genrl_gauss_kl_fwd(_p(lm), _p(ls), _p(rm), _p(rs), _p(kl), None, None, R, S, _stream()), 'gauss_kl_fwd')
-        loss = torch.empty((), device=lm.device)
-        check(lib().genrl_kl_balance_fwd(_p(kl), R, mix, free, _p(loss), _stream()), 'kl_balance_fwd')
-        ctx.save_for_backward(lm, ls, rm, rs, kl)
-        ctx.mix, ctx.free = mix, free
+        loss, mean = _kl_loss_fwd(kl, R, mode, mix, free)
+        ctx.save_for_backward(lm, ls, rm, rs, kl, mean)
+        ctx.mix, ctx.free, ctx.mode = mix, free, mode
         value = kl.reshape(lm.shape[:-1])
         if tm:
             value = value.transpose(0, 1)
@@ -2635,14 +2653,12 @@ class _GaussKLBalance(Function):
 
     @staticmethod
     def backward(ctx, gloss, _gvalue):
-        lm, ls, rm, rs, kl = ctx.saved_tensors
+        lm, ls, rm, rs, kl, mean = ctx.saved_tensors
         if gloss is None:
-            return None, None, None, None, None, None
+            return None, None, None, None, None, None, None
         S = lm.shape[-1]
         R = kl.numel()
-        gp = torch.empty(R, device=lm.device); gq = torch.empty(R, device=lm.device)
-        check(lib().genrl_kl_balance_bwd(_p(kl), _p(gloss.contiguous()), R, ctx.mix, ctx.free, _p(gp), _p(gq), _stream()),
-              'kl_balance_bwd')
+        gp, gq = _kl_loss_bwd(kl, mean, gloss, ctx.mode, ctx.mix, ctx.free)
         need = ctx.needs_input_grad
         outs = [torch.empty_like(t) if need[i] else None for i, t in enumerate((lm, ls, rm, rs))]
         if any(o is not None for o in outs):
@@ -2650,12 +2666,12 @@ class _GaussKLBalance(Function):
                                            _p(outs[3]), R, S, _stream()), 'gauss_kl_bwd')
         if ctx.tm:
             outs = [o.transpose(0, 1) if o is not None else None for o in outs]
-        return outs[0], outs[1], outs[2], outs[3], None, None
+        return outs[0], outs[1], outs[2], outs[3], None, None, None
 
 
-def gauss_kl_balance(lhs_mean, lhs_std, rhs_mean, rhs_std, mix, free):
-    """EnsembleRSSM.kl_loss on Normal latents (balance != 0.5, free_avg False) -> (scalar loss, per-row KL value [detached])"""
-    return _GaussKLBalance.apply(lhs_mean, lhs_std, rhs_mean, rhs_std, float(mix), float(free))
+def gauss_kl_balance(lhs_mean, lhs_std, rhs_mean, rhs_std, mix, free, mode='balanced'):
+    """EnsembleRSSM.kl_loss on Normal latents -> (scalar loss, per-row KL value [detached]); mode: a name of KL_MODES"""
+    return _GaussKLBalance.apply(lhs_mean, lhs_std, rhs_mean, rhs_std, float(mix), float(free), KL_MODES[mode])
 
 
 def gauss_entropy(std):

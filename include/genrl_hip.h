@@ -552,6 +552,22 @@ int genrl_cat_kl_bwd(const float* lp, const float* lq, const float* gp, const fl
 int genrl_kl_balance_fwd(const float* kl, long R, float mix, float free_nats, float* loss, void* stream);
 int genrl_kl_balance_bwd(const float* kl, const float* gloss, long R, float mix, float free_nats, float* gp, float* gq,
                          void* stream);
+/* The same loss in every mode of the reference's kl_loss (:542-554) -- the GENRL_KL_* below, picked from `kl.balance` / `kl.free_avg`:
+ *   BALANCED    the pair above, bit for bit;
+ *   UNBALANCED  (balance == 0.5) loss = mean(max(kl,free)): one KL with its full gradient into both sides, gp = gq = the row's
+ *               gradient; mix is not read;
+ *   FREE_AVG    (free_avg) loss = mix*max(mean(kl),free) + (1-mix)*max(mean(kl),free): the clamp acts on the mean; every row gets
+ *               mix*gloss/R (gp) and (1-mix)*gloss/R (gq) when the mean lies above free, exact zeros when below.
+ * torch.maximum's tie rule holds in all of them: half the gradient at kl == free (FREE_AVG: at mean == free).  fwd is one workgroup
+ * with a fixed summation order and also writes mean(kl) to the device scalar `mean` (NULL: not written; FREE_AVG needs it), which
+ * bwd reads in FREE_AVG (there `kl` may be NULL) -- no mode is decided on the host.  bwd writes every element of gp and gq.  An
+ * unknown mode, R < 1 or a NULL the mode needs returns 1 before any launch. */
+#define GENRL_KL_BALANCED 0
+#define GENRL_KL_UNBALANCED 1
+#define GENRL_KL_FREE_AVG 2
+int genrl_kl_loss_fwd(const float* kl, long R, int mode, float mix, float free_nats, float* loss, float* mean, void* stream);
+int genrl_kl_loss_bwd(const float* kl, const float* mean, const float* gloss, long R, int mode, float mix, float free_nats,
+                      float* gp, float* gq, void* stream);
 
 /* ---- TwoHotDist (agent/dreamer_utils.py:120-171): mode 0 log_prob(x), mode 1 mean.  logits rows are `ld` floats
  * apart (255, or 256 for the padded rows the head's GEMMs prefer), dlogits rows `ldd`; with ldd > 255 the
