@@ -193,7 +193,8 @@ class WorldModel(Module):  # ref :120-321
         with torch.no_grad():
             for p in self.heads['reward']._out.parameters():
                 p.data = p.data * 0
-        assert not config.pred_discount, 'discount head is not on the GenRL path (conf/env/dmc_pixels.yaml:6)'
+        if config.pred_discount:                 # ref :147-148 (`discount_head.dist: binary`: a one-wide BinaryDist)
+            self.heads['discount'] = common.MLP(self.inp_size, (1,), **config.discount_head)
         for name in config.grad_heads:
             assert name in self.heads, name
         self.grad_heads = config.grad_heads
@@ -381,6 +382,16 @@ class WorldModel(Module):  # ref :120-321
             self._last_actor_raw = torch.stack(raws, 0)
         seq = _ImaginedSeq(rssm, seq)                  # 'feat' = cat(stoch, deter) (ref :272) on first access
         seq.planes = state_planes          # (planes of stoch / deter, rows h*N + n, from the fused rollout)
+        if 'discount' in self.heads:
+            # ref :274-286 with `.mean` for the `.mean()` of :275: the head over all H+1 rollout states in one evaluation, then
+            # one node for the head's mean, the replay buffer's flag in row 0, gamma and the cumulative weights.  The discounts stay
+            # attached: the lambda-returns carry a gradient through them into the rollout (the head's own weights are frozen here).
+            dhead = self.heads['discount']
+            raw = dhead._out.raw(dhead.trunk(_flat_stoch(seq['stoch'], seq['deter']), seq['deter'], planes=_state_planes(seq)))
+            term = is_terminal.reshape(-1).float() if is_terminal is not None else None
+            seq['discount'], seq['weight'] = ops.imag_discount(raw, term, float(self.cfg.discount))
+            seq.unit_weight = False
+            return seq
         # no discount head (conf/env/dmc_pixels.yaml:6): discount = gamma everywhere and weight = cumprod(ones) = 1
         # (ref :274-286) -- constants, built once per shape instead of five launches per update
         shape = tuple(seq['deter'].shape[:-1]) + (1,)
@@ -601,7 +612,10 @@ class ActorCritic(Module):  # ref :323-462
         # lambda_return(reward[:-1], value[:-1], bootstrap=value[-1]) (ref :446-449) on the unsliced tensors: the
         # slices + re-concatenation are three copies forward and three backward otherwise
         assert not isinstance(self.cfg.discount, torch.Tensor)
-        target = ops.lambda_return(reward, value, float(self.cfg.discount), float(self.cfg.discount_lambda))
+        if getattr(seq, 'unit_weight', False):
+            target = ops.lambda_return(reward, value, float(self.cfg.discount), float(self.cfg.discount_lambda))
+        else:           # learned discounts (`pred_discount`): a discount per step and column, which receives a gradient too
+            target = ops.lambda_return_disc(reward, value, disc, float(self.cfg.discount_lambda))
         metrics = {'critic_slow': ops.wmean(value.detach(), None, 1.0), 'critic_target': ops.wmean(target.detach(), None, 1.0)}
         return target, metrics, value[:-1]
 

@@ -7,7 +7,7 @@ of libgenrl_hip.so (genrl_amd/ops.py).  nn.Module containers (nn.Linear, nn.Conv
 are used only as *parameter holders*: their torch forward is never called on the hot path.
 
 What the GenRL path and the dreamer_v3 / dreamer_v2 defaults configure is implemented (norm 'layer'/'none', act SiLU / ELU, discrete or
-continuous latents, GRU cell, dists mse / twohot / normal / trunc_normal / tanh_normal / onehot / symlog_mse, image_dist mse / normal_unit_std, vector
+continuous latents, GRU cell, dists mse / twohot / normal / trunc_normal / tanh_normal / onehot / symlog_mse / binary, image_dist mse / normal_unit_std, vector
 observation keys beside or instead of one image key); other reference options raise.
 """
 import contextlib
@@ -88,6 +88,27 @@ class MSEHeadDist:
         if self._mode.shape[-1] == 1:
             return ops.sqerr_like(self._mode, value)
         return ops.vec_like(self._mode, value.float(), ops.VEC_LIKE_KINDS['mse'])       # (a decoder's vector key)
+
+
+class BinaryDist:
+    """DistLayer 'binary' (ref :820-823) on a one-wide head: Independent(BernoulliDist(sigmoid(x)), 1), whose first positional parameter is
+    `logits` (ref :199-201) -- so the distribution is Bernoulli(logits = z) with z = sigmoid(x).  Restated as the reference computes it:
+    log_prob(t) = t z - softplus(z), mean = sigmoid(z) in (0.5, 0.731), so the mode is 1."""
+    def __init__(self, raw):
+        assert raw.shape[-1] == 1, raw.shape
+        self._raw = raw
+
+    @property
+    def mean(self):
+        return torch.sigmoid(torch.sigmoid(self._raw))
+
+    def mode(self):
+        p = self.mean             # (torch's Bernoulli.mode: probs >= 0.5, NaN at the tie, which a z below 2^-24 rounds the mean to)
+        return torch.where(p == 0.5, torch.full_like(p, float('nan')), (p >= 0.5).to(p.dtype))
+
+    def log_prob(self, value):
+        assert self._raw.numel() == value.numel(), (self._raw.shape, value.shape)
+        return ops.binary_like(self._raw, value.float())
 
 
 class SymlogDist:
@@ -361,8 +382,19 @@ class _OneHotHead(_Head):
         return OneHotDist(raw.float(), site='actor', independent=False)
 
 
+class _BinaryHead(_Head):
+    """'binary': the discount head of `pred_discount: True` (BinaryDist), one-wide"""
+    def __init__(self, layer):
+        if int(np.prod(layer._shape)) != 1:
+            raise NotImplementedError(f'a binary head of shape {tuple(layer._shape)}: the discount head is one-wide')
+        self.layer = layer
+
+    def dist(self, raw):
+        return BinaryDist(raw)
+
+
 HEADS = {'mse': _MSEHead, 'twohot': _TwoHotHead, 'normal': _NormalHead, 'trunc_normal': lambda layer: _NormalHead(layer, trunc=True),
-         'tanh_normal': _TanhNormalHead, 'onehot': _OneHotHead, 'symlog_mse': _SymlogMSEHead}
+         'tanh_normal': _TanhNormalHead, 'onehot': _OneHotHead, 'symlog_mse': _SymlogMSEHead, 'binary': _BinaryHead}
 
 
 # ----------------------------------------------------------------------------- scans (API parity)

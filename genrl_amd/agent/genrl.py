@@ -42,6 +42,9 @@ class GenRLAgent(DreamerAgent):
         if not cfg.rssm.get('discrete', False) or not cfg.connector_rssm.get('discrete', False):
             raise NotImplementedError('GenRLAgent needs discrete latents (`rssm.discrete`, `connector_rssm.discrete`): its connector '
                                       'teacher-forces one-hot latents; continuous latents are built for DreamerAgent and Plan2Explore')
+        if cfg.get('pred_discount', False):
+            raise NotImplementedError('GenRLAgent is built without the discount head (conf/env/dmc_pixels.yaml:6): `pred_discount: True` '
+                                      'is built for DreamerAgent and Plan2Explore')
         for part in ('encoder', 'decoder'):
             vec = [k for k, v in kwargs['obs_space'].items() if len(v.shape) == 1 and re.match(cfg[part].get('mlp_keys', r'.*'), k)]
             if vec:

@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = ['gemm.hip', 'gemm_planes.hip', 'gemm_planes_tn.hip', 'rowops.hip', 'dist.hip', 'conv.hip', 'optim.hip', 'stats.hip', 'seq.hip', 'ensemble.hip',
-       'rowact.hip', 'discrete.hip', 'gaussian.hip', 'vecobs.hip', 'heads.hip']
+       'rowact.hip', 'discrete.hip', 'gaussian.hip', 'vecobs.hip', 'heads.hip', 'discount.hip']
 OUT = os.path.join(HERE, 'libgenrl_hip.so')
 OBJ = os.path.join(HERE, 'csrc', 'build')
 

@@ -35,6 +35,7 @@ def default_cfg(batch_size=32, batch_length=32, device='cuda', task='stickman_wa
         img_size=64,
         rssm=dict(rssm, single_obs_posterior=True),
         reward_head=dict(layers=4, units=1024, norm='layer', dist='twohot'),
+        discount_head=dict(layers=4, units=512, norm='none', dist='binary'),        # (read with `pred_discount: True` only)
         kl=dict(free=1.0, forward=False, balance=0.85, free_avg=False),
         loss_scales=dict(kl=0.6, reward=1.0, discount=1.0, proprio=1.0),
         model_opt=dict(opt='adam', lr=1e-4, eps=1e-8, clip=1000, wd=1e-6),
@@ -97,6 +98,7 @@ def dreamer_v2_settings():
         rssm=dict(ensemble=1, hidden=512, deter=512, stoch=32, discrete=32, norm='none', std_act='softplus', min_std=0.1,
                   single_obs_posterior=False),
         reward_head=dict(layers=4, units=512, norm='none', dist='mse'),
+        discount_head=dict(layers=4, units=512, norm='none', dist='binary'),
         kl=dict(free=1.0, forward=False, balance=0.8, free_avg=False),
         loss_scales=dict(kl=1.0, reward=1.0, discount=1.0, proprio=1.0),
         model_opt=dict(opt='adam', lr=3e-4, eps=1e-5, clip=1000, wd=1e-6),
@@ -114,7 +116,8 @@ def dreamer_cfg(batch_size=64, batch_length=50, device='cuda', task='walker_walk
     agent/dreamer.yaml (BASELINE configs[2]: DreamerAgent, walker A=6).  Overrides `discrete_actions=True` (one-hot actor head) and, with it,
     `actor_grad='reinforce'` select the discrete-action routes; both are passed through as given.  An `rssm` override with
     `discrete=False` (and `stoch`, `std_act` in softplus / sigmoid / sigmoid2, `min_std`) selects continuous latents.
-    `act='ELU'` in an override of `rssm`, `encoder`, `decoder`, `reward_head`, `actor` or `critic` (the `# act: elu` of the reference's
+    `pred_discount=True` adds the discount head of `discount_head` and learned discounts in imagination.
+    `act='ELU'` in an override of `rssm`, `encoder`, `decoder`, `reward_head`, `discount_head`, `actor` or `critic` (the `# act: elu` of the reference's
     files) gives that block ELU, each block on its own; any other name raises NotImplementedError at construction."""
     assert defaults in ('dreamer_v3', 'dreamer_v2'), defaults
     rssm = dict(ensemble=1, hidden=512, deter=512, stoch=32, discrete=32, norm='layer', std_act='softplus', min_std=0.1,
@@ -124,6 +127,7 @@ def dreamer_cfg(batch_size=64, batch_length=50, device='cuda', task='walker_walk
               'clip_add_noise', 'clip_lafite_noise', 'viclip_encode', 'imag_actor_grad'):
         cfg.pop(k, None)
     cfg.update(_ad(dict(rssm=rssm, reward_head=dict(layers=4, units=512, norm='layer', dist='twohot'),
+                        discount_head=dict(layers=4, units=512, norm='layer', dist='binary'),
                         decoder_inputs='feat', actor=dict(layers=4, units=512, norm='layer', dist='normal', min_std=0.1),
                         critic=dict(layers=4, units=512, norm='layer', dist='twohot'), imag_horizon=15,
                         grad_heads=['decoder', 'reward'], actor_ent=3e-4)))
@@ -170,7 +174,7 @@ def make_dreamer_agent(cfg, act_dim=6, img=64, vec_obs=None):
 
 def dreamer_tiny_overrides():
     r = dict(hidden=32, deter=32, stoch=4, discrete=4)
-    return dict(rssm=r, reward_head=dict(units=32), actor=dict(units=32), critic=dict(units=32),
+    return dict(rssm=r, reward_head=dict(units=32), discount_head=dict(units=32), actor=dict(units=32), critic=dict(units=32),
                 encoder=dict(cnn_depth=4), decoder=dict(cnn_depth=4))
 
 

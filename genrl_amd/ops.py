@@ -710,6 +710,101 @@ def lambda_return(reward, value, disc, lam):
     return _LambdaReturn.apply(reward, value, float(disc), float(lam))
 
 
+# ------------------------------------------------------------------ the learned discount of `pred_discount: True` (csrc/discount.hip)
+
+class _LambdaReturnDisc(Function):
+    """_LambdaReturn with a discount per step and column (the reference's tensor `pcont`, agent/dreamer_utils.py:228-253): the discounts
+    receive a gradient too"""
+    @staticmethod
+    def forward(ctx, reward, value, disc, lam):
+        Hv = value.shape[0]
+        H = Hv - 1
+        N = value.numel() // Hv
+        r = _f32(reward).contiguous(); v = _f32(value).contiguous(); d = _f32(disc).contiguous()
+        assert r.shape[0] in (H, H + 1) and r.numel() // r.shape[0] == N      # (H+1 rows: the last one is not read)
+        assert d.shape == r.shape, (d.shape, r.shape)
+        out = torch.empty((H,) + tuple(r.shape[1:]), device=r.device)
+        check(lib().genrl_lambda_return_disc_fwd(_p(r), _p(v), _p(d), _p(out), H, N, lam, _stream()), 'lambda_disc_fwd')
+        ctx.save_for_backward(v, d, out)
+        ctx.dims = (H, N, lam, value.shape, reward.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        v, d, out = ctx.saved_tensors
+        H, N, lam, vshape, rshape = ctx.dims
+        g = g.contiguous()
+        dr = torch.empty(rshape, device=g.device)
+        dv = torch.empty(vshape, device=g.device)
+        dd = torch.empty(rshape, device=g.device)
+        check(lib().genrl_lambda_return_disc_bwd(_p(g), _p(v), _p(d), _p(out), _p(dr), _p(dv), _p(dd), H, N, lam,
+                                                 int(rshape[0] == H + 1), _stream()), 'lambda_disc_bwd')
+        return dr, dv, dd, None
+
+
+def lambda_return_disc(reward, value, disc, lam):
+    """lambda_return on learned discounts: reward and disc (H,N,1) -- or both (H+1,N,1) with an unused last row --, value (H+1,N,1)
+    [value[-1] is the bootstrap] -> (H,N,1)"""
+    return _LambdaReturnDisc.apply(reward, value, disc, float(lam))
+
+
+class _ImagDiscount(Function):
+    @staticmethod
+    def forward(ctx, x, term, gamma):
+        H1 = x.shape[0]
+        N = x.numel() // H1
+        xx = _f32(x).contiguous()
+        tt = _f32(term).reshape(-1).contiguous() if term is not None else None
+        assert tt is None or tt.numel() == N, (tt.shape, x.shape)
+        disc, weight = torch.empty_like(xx), torch.empty_like(xx)
+        check(lib().genrl_imag_discount_fwd(_p(xx), _p(tt), H1, N, gamma, _p(disc), _p(weight), _stream()), 'imag_discount_fwd')
+        ctx.save_for_backward(xx)
+        ctx.args = (H1, N, gamma, tt is not None)
+        ctx.mark_non_differentiable(weight)
+        return disc, weight
+
+    @staticmethod
+    def backward(ctx, gdisc, _gweight):
+        xx, = ctx.saved_tensors
+        H1, N, gamma, term_given = ctx.args
+        dx = torch.empty_like(xx)
+        check(lib().genrl_imag_discount_bwd(_p(xx), _p(_f32(gdisc).contiguous()), int(term_given), H1, N, gamma, _p(dx), _stream()),
+              'imag_discount_bwd')
+        return dx, None, None
+
+
+def imag_discount(x, term, gamma):
+    """WorldModel.imagine's discounts and weights (agent/dreamer.py:274-286) from the discount head's raw output x (H+1,N,1) as one node:
+    p = sigmoid(sigmoid(x)), p[0] = 1 - term where term (N values: is_terminal of the start states, float) is given ->
+    (disc = gamma p, weight = cumprod(cat(1, p[:-1]))), both shaped like x; the weight carries no gradient"""
+    return _ImagDiscount.apply(x, None if term is None else term.detach(), float(gamma))
+
+
+class _BinaryLike(Function):
+    @staticmethod
+    def forward(ctx, x, target):
+        xx = _f32(x).contiguous(); t = _f32(target).contiguous()
+        assert xx.numel() == t.numel()
+        like = torch.empty_like(xx)
+        check(lib().genrl_binary_like_fwd(_p(xx), _p(t), _p(like), xx.numel(), _stream()), 'binary_like_fwd')
+        ctx.save_for_backward(xx, t)
+        return like
+
+    @staticmethod
+    def backward(ctx, g):
+        xx, t = ctx.saved_tensors
+        d = torch.empty_like(xx)
+        check(lib().genrl_binary_like_bwd(_p(xx), _p(t), _p(_f32(g).contiguous()), _p(d), xx.numel(), _stream()), 'binary_like_bwd')
+        return d, None
+
+
+def binary_like(x, target):
+    """BinaryDist(x).log_prob(target) of the one-wide discount head: x, target (..., 1) -> target z - softplus(z), z = sigmoid(x), of
+    shape (...)"""
+    assert x.shape[-1] == 1 and x.numel() == target.numel(), (x.shape, target.shape)
+    return _BinaryLike.apply(x, target.detach().reshape(x.shape)).squeeze(-1)
+
+
 # ------------------------------------------------------------------ small statistics / scalar losses (stats.hip)
 
 def moments(x):

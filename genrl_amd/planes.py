@@ -107,27 +107,40 @@ def invalidate(params=None):
         _epoch += 1
         return
     ids = {id(q) for q in params}
-    for key, ent in _wcache.items():
+    for key, ent in _wcache.copy().items():          # (a copy: see _live)
         if key[0] in ids:
             ent[0] = -1
-    for key, ent in _dcache.items():
+    for key, ent in _dcache.copy().items():
         if key[0] in ids:
             ent[0] = -1
+
+
+def _live(keep):
+    """[(key, entry, W)] of the cached weights that are alive and that keep(key, entry) selects.  The cache is walked on a copy, and W is
+    held for as long as the list is: a garbage collection may run at any allocation in between -- an agent that went away is usually a
+    cycle --, and the finalizers of its parameters then drop their entries from _wcache (a dictionary that changes size under its own
+    iterator raises) and leave dead weak references in the entries picked before."""
+    out = []
+    for key, ent in _wcache.copy().items():
+        W = ent[3]()
+        if W is not None and keep(key, ent):
+            out.append((key, ent, W))
+    return out
 
 
 def _split_entries(stale, stream):
     if not stale:
         return
     arr = (struct('genrl_split_desc') * len(stale))()
-    for d, ((_, transpose, c0, c1), ent) in zip(arr, stale):
-        W, P = ent[3](), ent[1]
+    for d, ((_, transpose, c0, c1), ent, W) in zip(arr, stale):
+        P = ent[1]
         # (addresses and scalars, one descriptor per stale weight: assigned directly, several times cheaper than ops.fill(); a name that is
         # no field raises all the same, _lib)
         d.src, d.ldx, d.R, d.Cn = W.data_ptr() + 4 * c0 * W.stride(1), W.stride(0), W.shape[0], c1 - c0
         d.out, d.ld_out, d.plane, d.inv, d.transpose = P.ptr(0), P.ld, P.plane, P.inv_ptr(0), int(transpose)
     check(lib().genrl_split_h2_batch(arr, len(stale), stream), 'split_h2_batch')
-    for _, ent in stale:
-        ent[0], ent[2] = _epoch, ent[3]().data_ptr()
+    for _, ent, W in stale:
+        ent[0], ent[2] = _epoch, W.data_ptr()
 
 
 def _refresh_stale(stream):
@@ -135,14 +148,14 @@ def _refresh_stale(stream):
     optimiser step all of a group's matrices are stale together, and the first one asked for brings the others along.
     (Weights used on another stream -- the connector's on the side stream -- are left to that stream: a refresh enqueued here
     would not be ordered before their use there.)"""
-    _split_entries([(key, ent) for key, ent in _wcache.items() if ent[0] != _epoch and ent[4] == stream and ent[3]() is not None], stream)
+    _split_entries(_live(lambda key, ent: ent[0] != _epoch and ent[4] == stream), stream)
 
 
 def refresh(params):
     """re-split the cached planes of these parameters NOW, on the current stream (a change made outside a captured iteration
     -- the slow-critic copy between two graph replays -- cannot wait for a refresh that the captured graph may not contain)"""
     ids = {id(q) for q in params}
-    _split_entries([(key, ent) for key, ent in _wcache.items() if key[0] in ids and ent[3]() is not None], _stream())
+    _split_entries(_live(lambda key, ent: key[0] in ids), _stream())
 
 
 def weight(W, transpose=False, c0=0, c1=None):

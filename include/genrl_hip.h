@@ -584,6 +584,30 @@ int genrl_lambda_return_fwd(const float* reward, const float* value, float* ret,
 int genrl_lambda_return_bwd(const float* gret, float* dreward, float* dvalue, int H, long N, float disc, float lam,
                             int zero_tail, void* stream);
 
+/* ---- the learned discount of `pred_discount: True` (csrc/discount.hip).  The head is DistLayer 'binary' (agent/dreamer_utils.py:
+ * 820-823): Independent(Bernoulli(logits = z), 1) with z = sigmoid(x) -- the reference hands the sigmoid to BernoulliDist's first
+ * parameter, `logits` (:199-201) --, restated as it computes: log_prob(t) = t z - softplus(z), mean = sigmoid(z).  Every entry: fp32,
+ * one thread per element or column, every output element written; a NULL among the required pointers or a count below 1 returns 1
+ * before any launch.
+ * like[i] = target[i] z - softplus(z);  dx[i] = glike[i] (target[i] - sigmoid(z)) z (1 - z).  Finite for every finite x. */
+int genrl_binary_like_fwd(const float* x, const float* target, float* like, long R, void* stream);
+int genrl_binary_like_bwd(const float* x, const float* target, const float* glike, float* dx, long R, void* stream);
+/* WorldModel.imagine's discounts (agent/dreamer.py:274-286) from the head's raw output x [H1,N] at the H1 rollout states:
+ * p[t] = sigmoid(sigmoid(x[t])), with p[0] = 1 - term where term [N] (is_terminal of the start states, as floats) is not NULL;
+ * disc[t] = gamma p[t]; weight[0] = 1, weight[t] = weight[t-1] p[t-1], multiplied in that order.  One launch.
+ * bwd: dx[t] = gdisc[t] gamma p (1 - p) z (1 - z); row 0 is exactly zero when term_given != 0.  The weight has no backward. */
+int genrl_imag_discount_fwd(const float* x, const float* term, int H1, long N, float gamma, float* disc, float* weight, void* stream);
+int genrl_imag_discount_bwd(const float* x, const float* gdisc, int term_given, int H1, long N, float gamma, float* dx, void* stream);
+/* lambda_return with a discount per step and column (a tensor `pcont`): R_t = r_t + d_t ((1-lam) v_{t+1} + lam R_{t+1}), R_H = v_H;
+ * reward [H,N], value [H+1,N], disc [H,N]; reward and disc may carry an unread row H.  With every d_t equal to `disc` of
+ * genrl_lambda_return_fwd / _bwd, ret, dreward and dvalue equal theirs bit for bit.
+ * bwd: a_t = g_t + d_{t-1} lam a_{t-1}; dreward_t = a_t; ddisc_t = a_t ((1-lam) v_{t+1} + lam R_{t+1}); dvalue_{t+1} = d_t (1-lam) a_t
+ * (t < H-1), d_{H-1} a_{H-1} (bootstrap); dvalue_0 = 0.  zero_tail != 0: dreward and ddisc have H+1 rows, row H is zeroed. */
+int genrl_lambda_return_disc_fwd(const float* reward, const float* value, const float* disc, float* ret, int H, long N, float lam,
+                                 void* stream);
+int genrl_lambda_return_disc_bwd(const float* gret, const float* value, const float* disc, const float* ret, float* dreward,
+                                 float* dvalue, float* ddisc, int H, long N, float lam, int zero_tail, void* stream);
+
 /* ---- MSEDist.log_prob against uint8 frames (agent/dreamer_utils.py:74-83; agent/dreamer.py:294-295) */
 int genrl_mse_fwd(const float* mean, const uint8_t* obs, float* like, long Nimg, int E, void* stream);
 int genrl_mse_bwd(const float* mean, const uint8_t* obs, const float* glike, float* dmean, long Nimg, int E,
