@@ -598,6 +598,23 @@ class MLP(Module):  # ref :718-747
 
 # ----------------------------------------------------------------------------- encoder / decoder
 
+def _conv_norm(norm, depth):
+    """the norm module of a conv layer (ref :587, :669): ImgChLayerNorm for 'layer', NormLayer('none') for 'none' (no parameters: the layer is
+    conv + bias + act); any other name raises NotImplementedError(name), as the reference's NormLayer does"""
+    if norm == 'layer':
+        return ImgChLayerNorm(depth)
+    if norm != 'none':
+        raise NotImplementedError(norm)
+    return NormLayer('none', depth)
+
+
+def _conv_ln(norm_mod, act):
+    """the keywords a conv layer's node takes for its norm module: the fused channel-LayerNorm, or the activation alone"""
+    if isinstance(norm_mod, ImgChLayerNorm):
+        return dict(ln=(norm_mod.norm.weight, norm_mod.norm.bias, norm_mod.norm.eps, act))
+    return dict(ln=None, act=act)
+
+
 def _conv_sizes(size, kernels, transposed=False):
     out = []
     for k in kernels:
@@ -629,7 +646,9 @@ class Encoder(Module):  # ref :558-628
         self.cnn_keys = [k for k, v in shapes.items() if re.match(cnn_keys, k) and len(v) == 3]
         self.mlp_keys = [k for k, v in shapes.items() if re.match(mlp_keys, k) and len(v) == 1]
         self._act = _block_act(act)
-        assert norm == 'layer', 'layer norm (both default sets)'
+        if norm not in ('layer', 'none'):
+            raise NotImplementedError(norm)
+        self._norm = norm
         assert self.cnn_keys or self.mlp_keys, 'no observation key selected'
         self._cnn_depth, self._cnn_kernels = cnn_depth, cnn_kernels
         self._mlp_layers, self._symlog_inputs = list(mlp_layers), symlog_inputs
@@ -638,7 +657,7 @@ class Encoder(Module):  # ref :558-628
             for i, kernel in enumerate(self._cnn_kernels):
                 prev_depth = 3 if i == 0 else 2 ** (i - 1) * self._cnn_depth
                 depth = 2 ** i * self._cnn_depth
-                layers += [nn.Conv2d(prev_depth, depth, kernel, stride=2), ImgChLayerNorm(depth), get_act(act)]
+                layers += [nn.Conv2d(prev_depth, depth, kernel, stride=2), _conv_norm(norm, depth), get_act(act)]
             self._conv_model = nn.Sequential(*layers)
         if self.mlp_keys:           # ref :590-602; the first layer reads the keys side by side, in `shapes` order
             assert self._mlp_layers, 'vector keys need at least one MLP layer'
@@ -687,7 +706,7 @@ class Encoder(Module):  # ref :558-628
             # (an inner layer's fp32 activation has no reader when the next layer gathers from its planes forward AND backward: decided by
             # the next layer's own predicates, ops_conv_planes.consumer_reads_planes_only -- not by position)
             nxt = True if i == last else ('conv', self._cnn_kernels[i + 1])
-            x = conv2d(x, conv.weight, conv.bias, ln=(ln.norm.weight, ln.norm.bias, ln.norm.eps, self._act), fp32_out=nxt, planes_out=i != last)
+            x = conv2d(x, conv.weight, conv.bias, fp32_out=nxt, planes_out=i != last, **_conv_ln(ln, self._act))
         n, h, w, c = x.shape
         return ops.transpose_last2(x.reshape(n, h * w, c)).reshape(n, c * h * w)    # NCHW flatten, ref :621
 
@@ -701,7 +720,10 @@ class Decoder(Module):  # ref :631-715
         self.cnn_keys = [k for k, v in shapes.items() if re.match(cnn_keys, k) and len(v) == 3]
         self.mlp_keys = [k for k, v in shapes.items() if re.match(mlp_keys, k) and len(v) == 1]
         self._act = _block_act(act)
-        assert norm == 'layer' and image_dist in ('mse', 'normal_unit_std')
+        if norm not in ('layer', 'none'):
+            raise NotImplementedError(norm)
+        self._norm = norm
+        assert image_dist in ('mse', 'normal_unit_std')
         self._image_dist = image_dist
         assert len(self.cnn_keys) <= 1 and (self.cnn_keys or self.mlp_keys), 'one image key at most, and at least one key'
         self._cnn_depth, self._cnn_kernels = cnn_depth, cnn_kernels
@@ -716,7 +738,7 @@ class Decoder(Module):  # ref :631-715
                 if last:
                     depth = sum(self.channels.values())
                 layers += [nn.ConvTranspose2d(prev_depth, depth, kernel, stride=2),
-                           NormLayer('none', depth) if last else ImgChLayerNorm(depth),
+                           NormLayer('none', depth) if last else _conv_norm(norm, depth),
                            nn.Identity() if last else get_act(act)]
             self._conv_model = nn.Sequential(*layers)
         if self.mlp_keys:           # ref :672-684: one trunk on the features, one DistLayer per vector key
@@ -752,7 +774,7 @@ class Decoder(Module):  # ref :631-715
                 # predicates say it reads planes only)
                 nconv = self._conv_model[3 * (i + 1)]
                 nxt = True if i == n - 2 else ('convT', nconv.out_channels, self._cnn_kernels[i + 1])
-                x = convT2d(x, conv.weight, conv.bias, ln=(ln.norm.weight, ln.norm.bias, ln.norm.eps, self._act), fp32_out=nxt, planes_out=i != n - 2)
+                x = convT2d(x, conv.weight, conv.bias, fp32_out=nxt, planes_out=i != n - 2, **_conv_ln(ln, self._act))
             else:
                 x = ops.convT2d_s2(x, conv.weight, conv.bias, out_nchw=True)     # frames leave in the reference's NCHW
         image_dist = NormalUnitStdDist if self._image_dist == 'normal_unit_std' else MSEDist          # ref :704

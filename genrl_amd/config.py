@@ -118,7 +118,10 @@ def dreamer_cfg(batch_size=64, batch_length=50, device='cuda', task='walker_walk
     `discrete=False` (and `stoch`, `std_act` in softplus / sigmoid / sigmoid2, `min_std`) selects continuous latents.
     `pred_discount=True` adds the discount head of `discount_head` and learned discounts in imagination.
     `act='ELU'` in an override of `rssm`, `encoder`, `decoder`, `reward_head`, `discount_head`, `actor` or `critic` (the `# act: elu` of the reference's
-    files) gives that block ELU, each block on its own; any other name raises NotImplementedError at construction."""
+    files) gives that block ELU, each block on its own; any other name raises NotImplementedError at construction.
+    `norm='none'` in an override of `encoder` or `decoder` (norm_free_convs() sets both) makes that block's conv stack conv + bias + activation
+    without the channel-LayerNorm and its MLP stack bias-free Linear + activation, each block on its own; any name other than
+    'layer' / 'none' raises NotImplementedError at construction."""
     assert defaults in ('dreamer_v3', 'dreamer_v2'), defaults
     rssm = dict(ensemble=1, hidden=512, deter=512, stoch=32, discrete=32, norm='layer', std_act='softplus', min_std=0.1,
                 single_obs_posterior=False)
@@ -165,6 +168,12 @@ def vecobs_overrides(kind, key=None, mlp_layers=None):
     if mlp_layers is not None:
         enc['mlp_layers'], dec['mlp_layers'] = list(mlp_layers), list(mlp_layers)
     return dict(encoder=enc, decoder=dec)
+
+
+def norm_free_convs():
+    """the overrides of the norm-free conv encoder / decoder (the reference's class default, `norm: none`).  With
+    defaults='dreamer_v2' and `act='ELU'` in every block this is the DreamerV2 network as published"""
+    return dict(encoder=dict(norm='none'), decoder=dict(norm='none'))
 
 
 def make_dreamer_agent(cfg, act_dim=6, img=64, vec_obs=None):

@@ -250,6 +250,137 @@ __global__ __launch_bounds__(256) void ln_act_bwd_grp_kernel(const float* __rest
   }
 }
 
+// ------------------------------------------------------------------ norm-free conv layers: the activation alone over pixel rows
+// A conv layer WITHOUT a channel-LayerNorm (`encoder.norm: none` / `decoder.norm: none`: [Conv2d, NormLayer('none'), act], ref :587, :669):
+// y = act(x) over the M pixel rows of N channels, the bias already added by the product.  The same lane groups as the channel-LayerNorm
+// kernels above (GL lanes per row, one float4 each, 64 / GL consecutive rows per wave and iteration); a row wider than 4 GL floats (N > 256:
+// GL = 64) takes NV float4 per lane, 256 floats apart.  No parameter bounds the output, so the scale of its uniform planes is the tensor's
+// own maximum: every workgroup leaves the largest |y| it has produced in amax_part[blockIdx.x] and split_h2u_from_parts (a second launch)
+// reduces them and splits the stored y -- the bits of genrl_split_h2u on y, without its pass over y for the maximum.
+template <int GL, int NV, int ACT>
+__global__ __launch_bounds__(256) void chan_act_fwd_grp_kernel(const float* __restrict__ x, long ldx, float* __restrict__ y, long ldy,
+                                                               int M, int N, float* __restrict__ amax_part) {
+  constexpr int RPW = 64 / GL;
+  __shared__ float amx[4];
+  float am = 0.f;
+  const int lane = threadIdx.x & 63, gl = lane % GL, gi = lane / GL, w = threadIdx.x >> 6;
+  const long wave = (long)blockIdx.x * 4 + w, nwaves = (long)gridDim.x * 4;
+  for (long r = wave * RPW + gi; r < M; r += nwaves * RPW) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      const int c = (j * GL + gl) * 4;
+      if (c < N) {
+        const float4 v = ld4(x + r * ldx + c);
+        const float4 z = make_float4(act_apply(v.x, ACT), act_apply(v.y, ACT), act_apply(v.z, ACT), act_apply(v.w, ACT));
+        st4(y + r * ldy + c, z);
+        am = fmaxf(am, h2_amax4(z));
+      }
+    }
+  }
+  if (amax_part) {
+    am = wave_max(am);
+    if (lane == 0) amx[w] = am;
+    __syncthreads();
+    if (threadIdx.x == 0) amax_part[blockIdx.x] = fmaxf(fmaxf(amx[0], amx[1]), fmaxf(amx[2], amx[3]));
+  }
+}
+
+// dx = dy act'(x); part (or NULL): [gridDim.x][N] column sums of the workgroup's dx rows (the conv bias gradient; summed in a fixed order by
+// reduce_cols); amax_part as in the forward
+template <int GL, int NV, int ACT>
+__global__ __launch_bounds__(256) void chan_act_bwd_grp_kernel(const float* __restrict__ dy, long lddy, const float* __restrict__ x,
+                                                               long ldx, float* __restrict__ dx, long lddx, float* __restrict__ part,
+                                                               int M, int N, float* __restrict__ amax_part) {
+  constexpr int RPW = 64 / GL;
+  __shared__ float4 sm[4][NV][GL];
+  __shared__ float amx[4];
+  float am = 0.f;
+  const int lane = threadIdx.x & 63, gl = lane % GL, gi = lane / GL, w = threadIdx.x >> 6;
+  const long wave = (long)blockIdx.x * 4 + w, nwaves = (long)gridDim.x * 4;
+  float4 ac[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) ac[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (long r = wave * RPW + gi; r < M; r += nwaves * RPW) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      const int c = (j * GL + gl) * 4;
+      if (c < N) {
+        const float4 xv = ld4(x + r * ldx + c), dv = ld4(dy + r * lddy + c);
+        const float4 o = make_float4(dv.x * act_grad(xv.x, ACT), dv.y * act_grad(xv.y, ACT), dv.z * act_grad(xv.z, ACT),
+                                     dv.w * act_grad(xv.w, ACT));
+        st4(dx + r * lddx + c, o);
+        am = fmaxf(am, h2_amax4(o));
+        ac[j].x += o.x; ac[j].y += o.y; ac[j].z += o.z; ac[j].w += o.w;
+      }
+    }
+  }
+  if (amax_part) {
+    am = wave_max(am);
+    if (lane == 0) amx[w] = am;
+    __syncthreads();
+    if (threadIdx.x == 0) amax_part[blockIdx.x] = fmaxf(fmaxf(amx[0], amx[1]), fmaxf(amx[2], amx[3]));
+  }
+  if (!part) return;
+  // lanes with the same columns (gl) across the RPW row groups of the wave, then the 4 waves through LDS
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+#pragma unroll
+    for (int o = GL; o < 64; o <<= 1) {
+      ac[j].x += __shfl_xor(ac[j].x, o, 64);
+      ac[j].y += __shfl_xor(ac[j].y, o, 64);
+      ac[j].z += __shfl_xor(ac[j].z, o, 64);
+      ac[j].w += __shfl_xor(ac[j].w, o, 64);
+    }
+    if (gi == 0) sm[w][j][gl] = ac[j];
+  }
+  __syncthreads();
+  if (threadIdx.x < GL) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      const int c = (j * GL + gl) * 4;
+      if (c < N) {
+        const float4 a0 = sm[0][j][gl], a1 = sm[1][j][gl], a2 = sm[2][j][gl], a3 = sm[3][j][gl];
+        st4(part + (long)blockIdx.x * N + c, make_float4(a0.x + a1.x + a2.x + a3.x, a0.y + a1.y + a2.y + a3.y,
+                                                        a0.z + a1.z + a2.z + a3.z, a0.w + a1.w + a2.w + a3.w));
+      }
+    }
+  }
+}
+
+// the scalar arm: any N, any row spacing, any alignment; no planes
+__global__ __launch_bounds__(256) void chan_act_fwd_scalar_kernel(const float* __restrict__ x, long ldx, float* __restrict__ y, long ldy,
+                                                                  long M, int N, int act) {
+  const long n = M * N;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const long r = i / N; const int c = (int)(i % N);
+    y[r * ldy + c] = act_apply(x[r * ldx + c], act);
+  }
+}
+// 64 columns x 4 interleaved row subsets per workgroup over a chunk of rows (colsum_partial_kernel's shape): dx and, with part != NULL,
+// part[blockIdx.y][N]
+__global__ __launch_bounds__(256) void chan_act_bwd_scalar_kernel(const float* __restrict__ dy, long lddy, const float* __restrict__ x,
+                                                                  long ldx, float* __restrict__ dx, long lddx, float* __restrict__ part,
+                                                                  int M, int N, int act, int rows_per_chunk) {
+  __shared__ float sm[4][64];
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int sub = threadIdx.x >> 6;
+  const int r0 = blockIdx.y * rows_per_chunk, r1 = min(M, r0 + rows_per_chunk);
+  float a = 0.f;
+  if (c < N)
+    for (int r = r0 + sub; r < r1; r += 4) {
+      const float o = dy[(long)r * lddy + c] * act_grad(x[(long)r * ldx + c], act);
+      dx[(long)r * lddx + c] = o;
+      a += o;
+    }
+  if (!part) return;
+  sm[sub][threadIdx.x & 63] = a;
+  __syncthreads();
+  if (sub == 0 && c < N) {
+    const int l = threadIdx.x;
+    part[(long)blockIdx.y * N + c] = sm[0][l] + sm[1][l] + sm[2][l] + sm[3][l];
+  }
+}
+
 // out[j] (+)= sum_c part[c][j]
 __global__ void reduce_chunks_kernel(const float* __restrict__ part, float* __restrict__ out, int nchunk,
                                      long n, int accumulate) {
@@ -1584,6 +1715,81 @@ int genrl_ln_act_bwd_h2u(const float* dy, long lddy, const float* x, long ldx, c
   if (!dxp || !inv || !amax_ws || !dx) return GENRL_EINVAL;
   return ln_act_bwd_impl(dy, lddy, x, ldx, gamma, beta, mean, rstd, dx, lddx, dgamma, dbeta, dcolsum, ws, M, N, act,
                          accumulate_params, PlaneOut{dxp, ldp, plane, inv}, stream, amax_ws);
+}
+
+/* ---- norm-free conv layers (chan_act_*_kernel): y = act(x) / dx = dy act'(x), db (+)= column sums of dx, optional UNIFORM planes of the
+ * output through the kernel's per-workgroup maxima (amax_ws >= 2048 floats) and split_h2u_from_parts */
+#define LAUNCH_CHAN(KERNEL, GLV, NVV, ACT, GRID, S, ...)                                                                             \
+  do {                                                                                                                              \
+    if ((ACT) == GENRL_ACT_ELU) hipLaunchKernelGGL((KERNEL<GLV, NVV, GENRL_ACT_ELU>), dim3(GRID), dim3(256), 0, S, __VA_ARGS__);    \
+    else hipLaunchKernelGGL((KERNEL<GLV, NVV, GENRL_ACT_SILU>), dim3(GRID), dim3(256), 0, S, __VA_ARGS__);                          \
+  } while (0)
+#define CHAN_DISPATCH(KERNEL, N, ...)                                                                                               \
+  do {                                                                                                                              \
+    if ((N) <= 64) LAUNCH_CHAN(KERNEL, 16, 1, __VA_ARGS__);                                                                         \
+    else if ((N) <= 128) LAUNCH_CHAN(KERNEL, 32, 1, __VA_ARGS__);                                                                   \
+    else if ((N) <= 256) LAUNCH_CHAN(KERNEL, 64, 1, __VA_ARGS__);                                                                   \
+    else if ((N) <= 512) LAUNCH_CHAN(KERNEL, 64, 2, __VA_ARGS__);                                                                   \
+    else if ((N) <= 768) LAUNCH_CHAN(KERNEL, 64, 3, __VA_ARGS__);                                                                   \
+    else LAUNCH_CHAN(KERNEL, 64, 4, __VA_ARGS__);                                                                                   \
+  } while (0)
+constexpr int CHAN_MAX_N = 1024;           // widest row of the lane-group arm (4 float4 per lane of a 64-lane group)
+static inline int chan_gl(int N) { return N <= 64 ? 16 : (N <= 128 ? 32 : 64); }
+static inline bool chan_act_code_ok(int act) { return act == GENRL_ACT_SILU || act == GENRL_ACT_ELU; }
+
+int genrl_chan_act_fwd_h2u(const float* x, long ldx, float* y, long ldy, int M, int N, int act, uint16_t* yp, long ldp, long plane,
+                           float* inv, float* amax_ws, void* stream) {
+  GENRL_ENTER();
+  if (!chan_act_code_ok(act)) return GENRL_EINVAL;
+  if (M <= 0) return GENRL_OK;
+  if (!x || !y || N <= 0 || ldx < N || ldy < N) return GENRL_EINVAL;
+  const bool vec = N <= CHAN_MAX_N && (N & 3) == 0 && (ldx & 3) == 0 && (ldy & 3) == 0 && aligned16(x) && aligned16(y);
+  if (yp && (!vec || !inv || !amax_ws || (ldp & 3) || ldp < N)) return GENRL_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  if (!vec) {
+    const int grid = (int)std::min<long>(cdiv((long)M * N, 256 * 4), 2048);
+    hipLaunchKernelGGL(chan_act_fwd_scalar_kernel, dim3(grid), dim3(256), 0, s, x, ldx, y, ldy, (long)M, N, act);
+    GENRL_CHECK_LAUNCH();
+    return GENRL_OK;
+  }
+  const int grid = (int)std::min<long>(cdiv(M, 4 * (64 / chan_gl(N))), 2048);
+  float* amax = yp ? amax_ws : nullptr;
+  CHAN_DISPATCH(chan_act_fwd_grp_kernel, N, act, grid, s, x, ldx, y, ldy, M, N, amax);
+  GENRL_CHECK_LAUNCH();
+  return yp ? split_h2u_from_parts(y, ldy, M, N, PlaneOut{yp, ldp, plane, inv}, amax_ws, grid, stream) : GENRL_OK;
+}
+
+/* floats of `ws` for genrl_chan_act_bwd_h2u with db != NULL: one partial row per workgroup + the two-level reduction's 16 rows */
+long genrl_chan_act_bwd_ws_floats(int M, int N) {
+  if (M <= 0 || N <= 0) return 0;
+  return (long)(std::min(cdiv(M, 4), 2048) + 16) * N;
+}
+
+int genrl_chan_act_bwd_h2u(const float* dy, long lddy, const float* x, long ldx, float* dx, long lddx, float* db, float* ws,
+                           int accumulate, int M, int N, int act, uint16_t* dxp, long ldp, long plane, float* inv, float* amax_ws,
+                           void* stream) {
+  GENRL_ENTER();
+  if (!chan_act_code_ok(act)) return GENRL_EINVAL;
+  if (M <= 0) return GENRL_OK;
+  if (!dy || !x || !dx || N <= 0 || lddy < N || ldx < N || lddx < N || (db && !ws)) return GENRL_EINVAL;
+  const bool vec = N <= CHAN_MAX_N && (N & 3) == 0 && (lddy & 3) == 0 && (ldx & 3) == 0 && (lddx & 3) == 0 && aligned16(dy) &&
+                   aligned16(x) && aligned16(dx) && (!db || aligned16(ws));
+  if (dxp && (!vec || !inv || !amax_ws || (ldp & 3) || ldp < N)) return GENRL_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  float* part = db ? ws : nullptr;
+  int nparts;
+  if (!vec) {
+    nparts = chunks_for(M);
+    hipLaunchKernelGGL(chan_act_bwd_scalar_kernel, dim3(cdiv(N, 64), nparts), dim3(256), 0, s, dy, lddy, x, ldx, dx, lddx, part, M, N,
+                       act, cdiv(M, nparts));
+  } else {
+    nparts = narrow_grid_for(M, chan_gl(N));
+    float* amax = dxp ? amax_ws : nullptr;
+    CHAN_DISPATCH(chan_act_bwd_grp_kernel, N, act, nparts, s, dy, lddy, x, ldx, dx, lddx, part, M, N, amax);
+  }
+  if (db) reduce_cols(ws, ws + (long)nparts * N, db, nparts, N, accumulate ? 1 : 0, s);
+  GENRL_CHECK_LAUNCH();
+  return dxp ? split_h2u_from_parts(dx, lddx, M, N, PlaneOut{dxp, ldp, plane, inv}, amax_ws, nparts, stream) : GENRL_OK;
 }
 
 long genrl_colsum_ws_floats(int M, int N) { return (long)(chunks_for(M) + 16) * N; }

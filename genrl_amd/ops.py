@@ -1629,6 +1629,64 @@ def _ln_bwd_rows(dy2d, pre2d, gamma, beta, mean, rstd, bias=None, act=1):
     return (dpre, None, None, None) if direct else (dpre, g0, g1, g2)
 
 
+def _act_fwd_rows(pre2d, act, want_planes=False):
+    """a norm-free conv layer's activation over its pixel rows (genrl_chan_act_fwd_h2u; act: GENRL_ACT_* code 1 / 2) -> (y, uniform planes of
+    y or None).  The fp32 output is always written: the planes are split from the stored values with the tensor's own maximum, which the
+    kernel leaves per workgroup.  Planes from 64 rows up at N % 4 == 0 (wider than the lane-group kernels' 1024: a split of y afterwards)"""
+    M, N = pre2d.shape
+    y = torch.empty_like(pre2d)
+    P = None
+    if want_planes and N % 4 == 0 and M >= 64 and N <= 1024:
+        from . import planes
+        P = planes.Planes(M, N, pre2d.device, zero=False)
+        amax = torch.empty(2048, device=pre2d.device)
+        check(lib().genrl_chan_act_fwd_h2u(_p(pre2d), N, _p(y), N, M, N, act, P.ptr(), P.ld, P.plane, P.inv_ptr(), _p(amax), _stream()),
+              'chan_act_fwd_h2u')
+        P.uniform = True
+    else:
+        check(lib().genrl_chan_act_fwd_h2u(_p(pre2d), N, _p(y), N, M, N, act, None, 0, 0, None, None, _stream()), 'chan_act_fwd_h2u')
+        if want_planes and N % 4 == 0 and M >= 64:
+            from . import ops_conv_planes
+            P = ops_conv_planes._uniform_split(y)
+    return y, P
+
+
+def _act_bwd_rows(dy2d, pre2d, bias, act, want_planes=False, need_db=True):
+    """-> dpre = dy act'(pre), the bias gradient (column sums of dpre: None where added straight into the bias's flat gradient buffer, or
+    where nobody asked), uniform planes of dpre or None -- one pass (genrl_chan_act_bwd_h2u) + the fixed-order reduction of its partial rows"""
+    M, N = pre2d.shape
+    dev = pre2d.device
+    dpre = torch.empty_like(pre2d)
+    db = tgt = ws = None
+    if need_db and bias is not None:
+        tgt = _grad_buf(bias)
+        db = tgt if tgt is not None else torch.empty(N, device=dev)
+        ws = _ws(lib().genrl_chan_act_bwd_ws_floats(M, N), dev)
+    P = None
+    if want_planes and N % 4 == 0 and M >= 64 and N <= 1024:
+        from . import planes
+        P = planes.Planes(M, N, dev, zero=False)
+        amax = torch.empty(2048, device=dev)
+        check(lib().genrl_chan_act_bwd_h2u(_p(dy2d), N, _p(pre2d), N, _p(dpre), N, _p(db), _p(ws), int(tgt is not None), M, N, act,
+                                           P.ptr(), P.ld, P.plane, P.inv_ptr(), _p(amax), _stream()), 'chan_act_bwd_h2u')
+        P.uniform = True
+    else:
+        check(lib().genrl_chan_act_bwd_h2u(_p(dy2d), N, _p(pre2d), N, _p(dpre), N, _p(db), _p(ws), int(tgt is not None), M, N, act,
+                                           None, 0, 0, None, None, _stream()), 'chan_act_bwd_h2u')
+        if want_planes and N % 4 == 0 and M >= 64:
+            from . import ops_conv_planes
+            P = ops_conv_planes._uniform_split(dpre)
+    return dpre, (None if tgt is not None else db), P
+
+
+def _nf_code(ln, act):
+    """the activation code of a norm-free conv layer (ln None, act 'SiLU' / 'ELU'), 0 for a layer without one (act None) or with a LayerNorm"""
+    if ln is not None:
+        assert act is None, 'a fused channel-LayerNorm names its activation in ln[3]'
+        return 0
+    return 0 if act is None else act_layer_code(act)
+
+
 def _implicit_conv(img, C):
     """The GEMM can gather stride-2 patches itself when every patch segment is 16-byte addressable."""
     return img.dtype == torch.float32 and C % 4 == 0 and img.data_ptr() % 16 == 0
@@ -1638,7 +1696,7 @@ class _Conv2dS2(Function):
     """nn.Conv2d(k, stride 2) as patch-gather + GEMM.  x: f32 NHWC (N,H,W,C) or u8 NCHW (N,C,H,W)
     [preprocess fused]; Wp (Co, k*k*Ci) = weight permuted to (co, kh, kw, ci); returns NHWC."""
     @staticmethod
-    def forward(ctx, x, Wp, b, k, gamma=None, beta=None, eps=0.0, act=1):
+    def forward(ctx, x, Wp, b, k, gamma=None, beta=None, eps=0.0, act=1, nf_act=0):
         u8 = x.dtype == torch.uint8
         x = x.contiguous()
         if u8:
@@ -1658,9 +1716,14 @@ class _Conv2dS2(Function):
         ctx.fused_ln = gamma is not None
         ctx.bias = b
         ctx.act = act
+        ctx.nf_act = 0 if ctx.fused_ln else nf_act
         if ctx.fused_ln:           # channel-LayerNorm + SiLU / ELU of the layer (ImgChLayerNorm + act)
             out, mean, rstd = _ln_fwd_rows(y, gamma, beta, eps, act)
             ctx.save_for_backward(x, Wp, y, mean, rstd, gamma, beta)
+            return out.reshape(Nimg, Ho, Wo, Co)
+        if ctx.nf_act:             # a norm-free layer: the activation alone (NormLayer('none') + act)
+            out, _ = _act_fwd_rows(y, ctx.nf_act)
+            ctx.save_for_backward(x, Wp, y)
             return out.reshape(Nimg, Ho, Wo, Co)
         ctx.save_for_backward(x, Wp)
         return y.reshape(Nimg, Ho, Wo, Co)
@@ -1678,6 +1741,8 @@ class _Conv2dS2(Function):
         if ctx.fused_ln:
             pre, mean, rstd, gamma, beta = ctx.saved_tensors[2:]
             dy2, dg, dbe, db_ln = _ln_bwd_rows(dy2, pre, gamma, beta, mean, rstd, ctx.bias, ctx.act)
+        elif ctx.nf_act:
+            dy2, db_ln, _ = _act_bwd_rows(dy2, ctx.saved_tensors[2], ctx.bias, ctx.nf_act, need_db=ctx.needs_input_grad[2])
         if ctx.needs_input_grad[1]:
             dW = torch.empty(Co, K, device=dy.device)
             if _implicit_conv(x, C) and Co % 4 == 0:
@@ -1687,12 +1752,12 @@ class _Conv2dS2(Function):
                 sgemm(dy2, 1, Co, cols, 1, K, dW, K, None, Co, K, M)
                 del cols
         if ctx.needs_input_grad[2]:
-            db = db_ln if ctx.fused_ln else colsum(dy2)
+            db = db_ln if (ctx.fused_ln or ctx.nf_act) else colsum(dy2)
         if (not u8) and ctx.needs_input_grad[0]:
             dcols = torch.empty(M, K, device=dy.device)
             sgemm(dy2, Co, 1, Wp, 1, K, dcols, K, None, M, K, Co)     # dcols = dy W
             dx = _col2im(dcols, None, Nimg, Ho, Wo, C, k, Hi, Wi)
-        return dx, dW, db, None, dg, dbe, None, None
+        return dx, dW, db, None, dg, dbe, None, None, None
 
 
 def permuted(W):
@@ -1723,13 +1788,15 @@ class _PermuteWeight(Function):
         return transpose_last2_raw(g.contiguous()).reshape(W.shape)
 
 
-def conv2d_s2(x, W, b, ln=None, fp32_out=True, planes_out=True):
+def conv2d_s2(x, W, b, ln=None, fp32_out=True, planes_out=True, act=None):
     """W (Co,Ci,k,k) in the reference layout; permuted per call to (Co, kh*kw*Ci) (gradient flows back
-    through the permute).  ln = (gamma, beta, eps[, act]): channel-LayerNorm + SiLU (act 'ELU': ELU) fused into the same node."""
+    through the permute).  ln = (gamma, beta, eps[, act]): channel-LayerNorm + SiLU (act 'ELU': ELU) fused into the same node.
+    ln None with act 'SiLU' / 'ELU': a norm-free layer, conv + bias + activation in the same node; ln None, act None: the conv alone."""
     Co, Ci, k, _ = W.shape
+    nf = _nf_code(ln, act)
     Wp = _PermuteWeight.apply(W).reshape(Co, k * k * Ci)
     if ln is None:
-        return _Conv2dS2.apply(x, Wp, b, k)
+        return _Conv2dS2.apply(x, Wp, b, k, None, None, 0.0, 1, nf)
     return _Conv2dS2.apply(x, Wp, b, k, ln[0], ln[1], float(ln[2]), _ln_code(ln))
 
 
@@ -1754,13 +1821,13 @@ class _ConvT2dS2(Function):
     """nn.ConvTranspose2d(k, stride 2) as GEMM + gather-form col2im.  x NHWC (N,Hi,Wi,Ci);
     Wp (Ci, k*k*Co) = weight permuted to (ci, kh, kw, co); returns NHWC."""
     @staticmethod
-    def forward(ctx, x, Wp, b, k, gamma=None, beta=None, eps=0.0, out_nchw=False, act=1):
+    def forward(ctx, x, Wp, b, k, gamma=None, beta=None, eps=0.0, out_nchw=False, act=1, nf_act=0):
         x = _f32(x).contiguous()
         Nimg, Hi, Wi, Ci = x.shape
         Nw = Wp.shape[1]
         Co = Nw // (k * k)
         M = Nimg * Hi * Wi
-        assert not (out_nchw and gamma is not None)
+        assert not (out_nchw and (gamma is not None or nf_act))
         if Co <= 4 and k == 6 and Ci == 48 and CONVT_DIRECT and Wp.is_contiguous() and not _p16():
             # the 3-channel end of the decoder: gather form on the fp32 matrix cores, no cols matrix (genrl_convt_small_co_fwd)
             Ho, Wo = 2 * (Hi - 1) + k, 2 * (Wi - 1) + k
@@ -1778,9 +1845,14 @@ class _ConvT2dS2(Function):
         ctx.fused_ln = gamma is not None
         ctx.bias = b
         ctx.act = act
+        ctx.nf_act = 0 if ctx.fused_ln else nf_act
         if ctx.fused_ln:
             out, mean, rstd = _ln_fwd_rows(y.reshape(-1, Co), gamma, beta, eps, act)
             ctx.save_for_backward(x, Wp, y, mean, rstd, gamma, beta)
+            return out.reshape(y.shape)
+        if ctx.nf_act:
+            out, _ = _act_fwd_rows(y.reshape(-1, Co), ctx.nf_act)
+            ctx.save_for_backward(x, Wp, y)
             return out.reshape(y.shape)
         ctx.save_for_backward(x, Wp)
         return y
@@ -1796,6 +1868,10 @@ class _ConvT2dS2(Function):
         if ctx.fused_ln:
             pre, mean, rstd, gamma, beta = ctx.saved_tensors[2:]
             dy, dg, dbe, db_ln = _ln_bwd_rows(dy.reshape(-1, Co), pre.reshape(-1, Co), gamma, beta, mean, rstd, ctx.bias, ctx.act)
+            dy = dy.reshape(Nimg, Ho, Wo, Co)
+        elif ctx.nf_act:
+            dy, db_ln, _ = _act_bwd_rows(dy.reshape(-1, Co), ctx.saved_tensors[2].reshape(-1, Co), ctx.bias, ctx.nf_act,
+                                         need_db=ctx.needs_input_grad[2])
             dy = dy.reshape(Nimg, Ho, Wo, Co)
         implicit = _implicit_conv(dy, Co) and Ci % 4 == 0 and not ctx.out_nchw
         dx = dW = db = None
@@ -1814,7 +1890,7 @@ class _ConvT2dS2(Function):
             timed_end(gemm_profile, e0, M, Ci, Nw, 'kk/convt_direct_bwd')
             if ctx.needs_input_grad[2]:
                 db = _nchw_bias_grad(dy, ctx.bias)
-            return dx, dW, db, None, None, None, None, None
+            return dx, dW, db, None, None, None, None, None, None, None
         dcols = None if implicit else _im2col(dy, Nimg, Ho, Wo, Co, k, 1 if ctx.out_nchw else 0)   # (M, Nw) patch matrix of dy
         if ctx.needs_input_grad[0]:
             dx = torch.empty(M, Ci, device=dy.device)
@@ -1830,22 +1906,24 @@ class _ConvT2dS2(Function):
             else:
                 sgemm(x, 1, Ci, dcols, 1, Nw, dW, Nw, None, Ci, Nw, M)    # dW = x^T dcols
         if ctx.needs_input_grad[2]:
-            if ctx.fused_ln:
+            if ctx.fused_ln or ctx.nf_act:
                 db = db_ln
             elif ctx.out_nchw:
                 db = _nchw_bias_grad(dy, ctx.bias)
             else:
                 db = colsum(dy.reshape(-1, Co))
-        return dx, dW, db, None, dg, dbe, None, None, None
+        return dx, dW, db, None, dg, dbe, None, None, None, None
 
 
-def convT2d_s2(x, W, b, ln=None, out_nchw=False, fp32_out=True, planes_out=True):
+def convT2d_s2(x, W, b, ln=None, out_nchw=False, fp32_out=True, planes_out=True, act=None):
     """W (Ci,Co,k,k) in the reference layout; permuted per call to (Ci, kh*kw*Co).  out_nchw: (N,Co,Ho,Wo) output
-    (written that way by the overlap-add kernel; no LayerNorm fusion then)."""
+    (written that way by the overlap-add kernel; no LayerNorm fusion and no activation then).  ln None with act 'SiLU' / 'ELU': a norm-free
+    layer, transposed conv + bias + activation in the same node."""
     Ci, Co, k, _ = W.shape
+    nf = _nf_code(ln, act)
     Wp = _PermuteWeight.apply(W).reshape(Ci, k * k * Co)
     if ln is None:
-        return _ConvT2dS2.apply(x, Wp, b, k, None, None, 0.0, out_nchw)
+        return _ConvT2dS2.apply(x, Wp, b, k, None, None, 0.0, out_nchw, 1, nf)
     return _ConvT2dS2.apply(x, Wp, b, k, ln[0], ln[1], float(ln[2]), False, _ln_code(ln))
 
 

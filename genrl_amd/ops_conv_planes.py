@@ -295,7 +295,10 @@ class _Conv2dS2P(Function):
                     ctx.cols = cols          # (the frames' patch matrix serves the weight gradient again: 0.15 GB at c2, 0.8 GB at c4, of 288)
         if isinstance(fp32_out, tuple):       # the consumer's description: decided by ITS predicates, not by the layer's position
             fp32_out = not consumer_reads_planes_only(fp32_out, Nimg, Ho, Wo, Co)
-        out, mean, rstd, outp, lazy = _ln_fwd(y, gamma, beta, eps, want_planes=planes_out and M >= min_rows(), want_fp32=fp32_out, act=ctx.act)
+        if gamma is None:       # a norm-free layer: the activation alone; its fp32 output is always written (the uniform split reads the stored values)
+            (out, outp), mean, rstd, lazy = ops._act_fwd_rows(y, ctx.act, want_planes=planes_out and M >= min_rows()), None, None, None
+        else:
+            out, mean, rstd, outp, lazy = _ln_fwd(y, gamma, beta, eps, want_planes=planes_out and M >= min_rows(), want_fp32=fp32_out, act=ctx.act)
         holder.append(outp); holder.append(lazy)
         ctx.dims = (Nimg, Hi, Wi, C, k, u8)
         ctx.bias = b
@@ -317,7 +320,12 @@ class _Conv2dS2P(Function):
         kr = need_dx and M >= min_rows() and Co >= KR_MIN_K
         # (the LayerNorm backward's planes are uniform-scale whenever it makes them itself: Co <= 256)
         sp_maybe = need_dx and SUBPIXEL and _hl_on() and (k % 2 == 0 or SUBPIXEL_ODD) and Co % 8 == 0 and Co >= 48 and C % 4 == 0
-        dy2, dg, dbe, db, dyp = _ln_bwd(dy.reshape(M, Co).contiguous(), pre, gamma, beta, mean, rstd, ctx.bias, want_planes=tn or kr or sp_maybe, act=ctx.act)
+        if gamma is None:
+            dy2, db, dyp = ops._act_bwd_rows(dy.reshape(M, Co).contiguous(), pre, ctx.bias, ctx.act, want_planes=tn or kr or sp_maybe,
+                                             need_db=ctx.needs_input_grad[2])
+            dg = dbe = None
+        else:
+            dy2, dg, dbe, db, dyp = _ln_bwd(dy.reshape(M, Co).contiguous(), pre, gamma, beta, mean, rstd, ctx.bias, want_planes=tn or kr or sp_maybe, act=ctx.act)
         dx = dW = None
         if ctx.needs_input_grad[1]:
             dW = torch.empty(Co, K, device=dy.device)
@@ -389,8 +397,11 @@ class _ConvT2dS2P(Function):
         Ho, Wo = y.shape[1], y.shape[2]
         if isinstance(fp32_out, tuple):
             fp32_out = not consumer_reads_planes_only(fp32_out, Nimg, Ho, Wo, Co)
-        out, mean, rstd, outp, lazy = _ln_fwd(y.reshape(-1, Co), gamma, beta, eps, want_planes=planes_out and Nimg * Ho * Wo >= min_rows(),
-                                              want_fp32=fp32_out, act=ctx.act)
+        if gamma is None:       # a norm-free layer (see _Conv2dS2P)
+            (out, outp), mean, rstd, lazy = ops._act_fwd_rows(y.reshape(-1, Co), ctx.act, want_planes=planes_out and Nimg * Ho * Wo >= min_rows()), None, None, None
+        else:
+            out, mean, rstd, outp, lazy = _ln_fwd(y.reshape(-1, Co), gamma, beta, eps, want_planes=planes_out and Nimg * Ho * Wo >= min_rows(),
+                                                  want_fp32=fp32_out, act=ctx.act)
         holder.append(outp); holder.append(lazy)
         ctx.dims = (Nimg, Hi, Wi, Ci, Co, k)
         ctx.bias = b
@@ -408,8 +419,13 @@ class _ConvT2dS2P(Function):
         gather = _gather_ok(M, Co, k) and Ci % 4 == 0
         tn = gather and xp is not None and M % 64 == 0 and ctx.needs_input_grad[1]
         dgr = gather and ctx.needs_input_grad[0]
-        dyv, dg, dbe, db, dyp = _ln_bwd(dy.contiguous().reshape(-1, Co), pre.reshape(-1, Co), gamma, beta, mean, rstd, ctx.bias,
-                                       want_planes=tn or dgr, act=ctx.act)
+        if gamma is None:
+            dyv, db, dyp = ops._act_bwd_rows(dy.contiguous().reshape(-1, Co), pre.reshape(-1, Co), ctx.bias, ctx.act, want_planes=tn or dgr,
+                                             need_db=ctx.needs_input_grad[2])
+            dg = dbe = None
+        else:
+            dyv, dg, dbe, db, dyp = _ln_bwd(dy.contiguous().reshape(-1, Co), pre.reshape(-1, Co), gamma, beta, mean, rstd, ctx.bias,
+                                           want_planes=tn or dgr, act=ctx.act)
         dyv = dyv.reshape(Nimg, Ho, Wo, Co)
         implicit = ops._implicit_conv(dyv, Co) and Ci % 4 == 0
         dcols = None
@@ -439,26 +455,44 @@ class _ConvT2dS2P(Function):
         return dx, dW, db, None, dg, dbe, None, None, None, None, None, None
 
 
-def conv2d_s2(x, W, b, ln, fp32_out=True, planes_out=True):
+def _ln_args(ln, act):
+    """(gamma, beta, eps, activation code) of a layer's node: its fused channel-LayerNorm, or (None, None, 0.0, code) for a norm-free layer
+    (ln None, act 'SiLU' / 'ELU': ops._nf_code)"""
+    if ln is None:
+        return None, None, 0.0, ops._nf_code(ln, act)
+    assert act is None, 'a fused channel-LayerNorm names its activation in ln[3]'
+    return ln[0], ln[1], float(ln[2]), ops._ln_code(ln)
+
+
+def conv2d_s2(x, W, b, ln=None, fp32_out=True, planes_out=True, act=None):
     """ops.conv2d_s2 with the fused channel-LayerNorm; the output carries ._planes (uniform planes of its pixel rows) for the
     next layer when it was worth making them.  fp32_out False: the caller passes the output to another layer of this module only,
     which reads the planes (the fp32 values are then filled on demand: ._lazy); fp32_out = ('conv', k) / ('convT', Co, k): the NEXT
     layer's description -- the fp32 activation is skipped exactly when that layer's own predicates say it reads planes only
-    (consumer_reads_planes_only); planes_out False: nothing reads the planes"""
+    (consumer_reads_planes_only); planes_out False: nothing reads the planes.  ln None with act 'SiLU' / 'ELU': a norm-free layer (conv +
+    bias + activation), whose fp32 output is always written; ln None, act None: the conv alone, on ops.conv2d_s2"""
+    if ln is None and act is None:
+        _need_fp32(x, getattr(x, '_lazy', None), getattr(x, '_planes', None))
+        return ops.conv2d_s2(x, W, b)
     Co, Ci, k, _ = W.shape
+    gamma, beta, eps, code = _ln_args(ln, act)
     Wp = ops._PermuteWeight.apply(W).reshape(Co, k * k * Ci)
     holder = []
-    y = _Conv2dS2P.apply(x, Wp, b, k, ln[0], ln[1], float(ln[2]), getattr(x, '_planes', None), holder, (W,),
-                         (getattr(x, '_lazy', None), fp32_out, planes_out), ops._ln_code(ln))
+    y = _Conv2dS2P.apply(x, Wp, b, k, gamma, beta, eps, getattr(x, '_planes', None), holder, (W,),
+                         (getattr(x, '_lazy', None), fp32_out, planes_out), code)
     y._planes, y._lazy = holder if holder else (None, None)
     return y
 
 
-def convT2d_s2(x, W, b, ln, fp32_out=True, planes_out=True):
+def convT2d_s2(x, W, b, ln=None, fp32_out=True, planes_out=True, act=None):
+    if ln is None and act is None:
+        _need_fp32(x, getattr(x, '_lazy', None), getattr(x, '_planes', None))
+        return ops.convT2d_s2(x, W, b)
     Ci, Co, k, _ = W.shape
+    gamma, beta, eps, code = _ln_args(ln, act)
     Wp = ops._PermuteWeight.apply(W).reshape(Ci, k * k * Co)
     holder = []
-    y = _ConvT2dS2P.apply(x, Wp, b, k, ln[0], ln[1], float(ln[2]), getattr(x, '_planes', None), holder, (W,),
-                          (getattr(x, '_lazy', None), fp32_out, planes_out), ops._ln_code(ln))
+    y = _ConvT2dS2P.apply(x, Wp, b, k, gamma, beta, eps, getattr(x, '_planes', None), holder, (W,),
+                          (getattr(x, '_lazy', None), fp32_out, planes_out), code)
     y._planes, y._lazy = holder if holder else (None, None)
     return y

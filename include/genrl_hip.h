@@ -143,6 +143,23 @@ int genrl_ln_act_bwd_h2u(const float* dy, long lddy, const float* x, long ldx, c
                          const float* mean, const float* rstd, float* dx, long lddx, float* dgamma, float* dbeta, float* dcolsum,
                          float* ws, int M, int N, int act, int accumulate_params, uint16_t* dxp, long ldp, long plane, float* inv,
                          float* amax_ws, void* stream);
+/* A conv layer WITHOUT a channel-LayerNorm (`encoder.norm: none` / `decoder.norm: none`: Conv2d + bias, NormLayer('none'), act;
+ * agent/dreamer_utils.py:587, :669): the activation alone over M pixel rows of N channels, rows ld* floats apart.
+ * genrl_chan_act_fwd_h2u: y = act(x), act = GENRL_ACT_SILU or GENRL_ACT_ELU (any other code, 0 included: 1 before any launch).  With
+ * yp != NULL also UNIFORM planes of y: the launch leaves one partial maximum of |y| per workgroup in amax_ws (>= 2048 floats), a second
+ * launch reduces them and splits the stored y -- bit for bit what genrl_split_h2u makes of y; padding columns are written as zeros.
+ * genrl_chan_act_bwd_h2u: dx = dy act'(x) and, with db != NULL, db[n] (+)= sum_m dx[m][n] (the conv bias gradient; accumulate 1 adds
+ * into db) from per-workgroup partial rows in ws (>= genrl_chan_act_bwd_ws_floats(M, N) floats, 16-byte aligned) summed in a fixed order,
+ * no atomics; dxp != NULL: uniform planes of dx as in the forward.
+ * Rows of N <= 1024 floats with N % 4 == 0, ld* % 4 == 0 and 16-byte aligned pointers take the lane-group kernels (16 / 32 / 64 lanes per
+ * row for N <= 64 / 128 / wider); everything else takes a scalar arm, which has no planes (asking for them returns 1).  M <= 0 returns 0
+ * without a launch.  x and y (dy / x and dx) must not overlap. */
+int genrl_chan_act_fwd_h2u(const float* x, long ldx, float* y, long ldy, int M, int N, int act, uint16_t* yp, long ldp, long plane,
+                           float* inv, float* amax_ws, void* stream);
+long genrl_chan_act_bwd_ws_floats(int M, int N);
+int genrl_chan_act_bwd_h2u(const float* dy, long lddy, const float* x, long ldx, float* dx, long lddx, float* db, float* ws,
+                           int accumulate, int M, int N, int act, uint16_t* dxp, long ldp, long plane, float* inv, float* amax_ws,
+                           void* stream);
 /* The stride-2 convolution product on planes: C[m, n] (+)= sum_kk patch(m, kk) B[n, kk] (+ bias), the patch matrix of an NHWC image
  * (agent/dreamer_utils.py:604-621 forward; :686-706 input gradient of the transposed convolutions) gathered by the operand DMA
  * itself -- m = (image, oy, ox), kk = (kh k + kw) Cc + c, 16-byte chunks = 8 channels of one pixel.  img: UNIFORM-scale planes
