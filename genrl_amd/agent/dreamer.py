@@ -239,7 +239,8 @@ class WorldModel(Module):  # ref :120-321
         # stream (flush_pending=False here; WorldModel.update flushes after the fork).
         overlap = (getattr(self.cfg, 'overlap_detached', False)
                    and (common.Optimizer.grad_reduce is None or (common.Optimizer.overlap_under_dp and not graph.cutting()))
-                   and getattr(self.cfg, 'imag_reward_fn', None) is not None)
+                   and getattr(self.cfg, 'imag_reward_fn', None) is not None
+                   and len(self.detached_update_fns) > 0)          # (nothing to fork for: every added module trains end to end)
         ctx = streams.fork('detached') if overlap else contextlib.nullcontext()
         with ctx:
             for k in self.detached_update_fns:

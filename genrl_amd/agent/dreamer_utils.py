@@ -1250,6 +1250,30 @@ class Optimizer:
         while self._pending:
             self._finish(self._pending.pop(0))
 
+    def release(self, params):
+        """Stop stepping `params` (GenRLAgent.finetune_mode after a connector trained end to end, `connector.detached_post: False`: its
+        weights leave the world model's loss).  A group that holds some of them is rebuilt over its other parameters, which keep their
+        Adam moments and step count; the released ones keep their values in storage of their own, without a gradient buffer, and are
+        only decayed from then on, like every parameter that is handed in without being live."""
+        self.flush()
+        ids = {id(p) for p in params}
+        for i, g in enumerate(self._groups):
+            if not ids & {id(p) for p in g.params}:
+                continue
+            pl.invalidate(g.params)
+            old = {id(p): off for p, off in zip(g.params, g.offsets)}
+            for p in g.params:
+                if id(p) in ids:
+                    p.data, p.grad = p.data.clone(), None
+            new = FlatGroup([p for p in g.params if id(p) not in ids])
+            for p, off in zip(new.params, new.offsets):
+                k, o = p.numel(), old[id(p)]
+                new.m[off:off + k].copy_(g.m[o:o + k]); new.v[off:off + k].copy_(g.v[o:o + k])
+            new.step = g.step
+            new.step_dev.copy_(g.step_dev)
+            self._groups[i] = new
+        self._live_cache.clear()
+
     def _flat_owner(self, p):
         for g in self._groups:
             for q in g.params:

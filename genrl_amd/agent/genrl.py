@@ -82,6 +82,8 @@ class GenRLAgent(DreamerAgent):
         self._imag_behavior = behavior
 
     def finetune_mode(self):  # agent/genrl.py:56-60
+        if self.wm.e2e_update_fns:          # (a connector that trained end to end sat in the world model's Adam group: it leaves it)
+            self.wm.model_opt.release([p for k in self.wm.e2e_update_fns for p in getattr(self.wm, k).parameters()])
         self.wm.detached_update_fns, self.wm.e2e_update_fns = {}, {}
         self.wm.grad_heads.append('reward')
         self._acting_behavior = self._imag_behavior

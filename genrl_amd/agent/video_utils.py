@@ -77,8 +77,8 @@ class VideoSSM(common.EnsembleRSSM):
             # the reference's connector raises on it: its free_avg loss has shape [1] and VideoSSM.update adds it in place into a 0-d
             # tensor (agent/video_utils.py:195), so there is nothing to compare against
             raise NotImplementedError('`connector_kl.free_avg: True` is refused: the reference\'s connector raises on it (DESIGN 5o)')
-        assert not temporal_embeds and token_dropout == 0 and detached_post and learn_initial, \
-            'shipped connector configuration only (agent/genrl.yaml:15)'
+        if not 0 <= token_dropout < 1:
+            raise ValueError(f'`connector.token_dropout` is a probability below 1, not {token_dropout!r}')
         hidden, deter, norm, act_dim = kwargs['hidden'], kwargs['deter'], kwargs['norm'], kwargs['action_dim']
         self.n_frames = n_frames
         self.viclip_emb_dim = act_dim - n_frames
@@ -89,17 +89,25 @@ class VideoSSM(common.EnsembleRSSM):
         self.rescale_embeds, self.denoising_ae, self.learn_initial = rescale_embeds, denoising_ae, learn_initial
         if denoising_ae:
             self.aligner = UNetDenoiser(self.viclip_emb_dim, self.viclip_emb_dim // 2, n_layers=2, norm='layer', act='SiLU')
-        mlp = [nn.Linear(act_dim, hidden), common.NormLayer(norm, hidden), common.get_act('SiLU'),
-               nn.Linear(hidden, hidden), common.NormLayer(norm, hidden), common.get_act('SiLU'),
-               nn.Linear(hidden, deter)]
-        self.initial_state_pred = nn.Sequential(*mlp)          # learned deter_0 from the first "action"
+        if learn_initial:                                          # (:88-95; without it initial() is the zero state)
+            mlp = [nn.Linear(act_dim, hidden), common.NormLayer(norm, hidden), common.get_act('SiLU'),
+                   nn.Linear(hidden, hidden), common.NormLayer(norm, hidden), common.get_act('SiLU'),
+                   nn.Linear(hidden, deter)]
+            self.initial_state_pred = nn.Sequential(*mlp)          # learned deter_0 from the first "action"
         del self._obs_out, self._obs_dist                      # a connector has no observation posterior
 
     # ------------------------------------------------------------------ pieces
     def get_action(self, video_embed):
-        """The SSM's 'action' = [clip embedding (optionally x sqrt(E)) | n_frames zero slots]  (:114-125)."""
+        """The SSM's 'action' = [clip embedding (optionally x sqrt(E)) | n_frames slots]  (:114-125).  The slots are zeros, or with
+        `temporal_embeds` one_hot(t % n_frames), t the position along dimension 1 of what was handed in."""
         if self.rescale_embeds:
             video_embed = video_embed * self.clip_const
+        if self.temporal_embeds:
+            # (device arithmetic only: an indexed assignment copies its scalar from the host, which a hipGraph capture refuses)
+            B, T = video_embed.shape[:2]
+            t = torch.arange(T, device=video_embed.device)[:, None] % self.n_frames
+            slots = (t == torch.arange(self.n_frames, device=video_embed.device)[None]).to(video_embed.dtype)
+            return torch.cat([video_embed, slots[None].expand(B, T, self.n_frames)], dim=-1)
         pad = video_embed.new_zeros(*video_embed.shape[:-1], self.n_frames)
         return torch.cat([video_embed, pad], dim=-1)
 
@@ -138,7 +146,12 @@ class VideoSSM(common.EnsembleRSSM):
         (stoch_{-1}: the learned initial state).  actions_tm: (T,B,A)."""
         S, K = self._stoch, self._discrete
         first = self.initial(B, init_embed=actions_tm[0])
-        shifted = torch.cat([first['stoch'].reshape(1, B, S * K), post_stoch.reshape(B, T, S * K).transpose(0, 1)[:-1]], 0)
+        if self.token_dropout > 0:
+            # stoch_{t-1} times one keep flag per row and step, step 0 included (:178-179): `rand > p` on u = exp(-e), e ~ Exp(1)
+            e = noise.draw('exp', 'conn.drop', (T, B), actions_tm.device)
+            shifted, _ = ops.tf_inputs(first['stoch'].reshape(B, S * K), post_stoch.reshape(B, T, S * K), e, float(self.token_dropout))
+        else:
+            shifted = torch.cat([first['stoch'].reshape(1, B, S * K), post_stoch.reshape(B, T, S * K).transpose(0, 1)[:-1]], 0)
         x = common._dense_ln_silu(shifted.reshape(T * B, S * K), self._img_in[0], self._img_in[1],
                                   actions_tm.reshape(T * B, -1))
         deter = ops.gru_seq(x.reshape(T, B, -1), None, first['deter'], self._cell._layer.weight,
@@ -150,7 +163,7 @@ class VideoSSM(common.EnsembleRSSM):
         from that chunk's embedding (:197-205).  No gradient."""
         nf, G = self.n_frames, T // self.n_frames
         heads = lambda v: v.reshape(B, G, nf, *v.shape[2:])[:, 1:, 0].reshape(B * (G - 1), *v.shape[2:])
-        a = self.get_action(heads(embeds))
+        a = self.get_action(heads(embeds).unsqueeze(1))[:, 0]         # (length-1 sequences: frame slot 0, :198-201)
         state = self.initial(B * (G - 1), init_embed=a, site='conn.ikl_init_q')
         prior = self.img_step(state, a, site='conn.ikl_step_q')
         return ops.wmean(self.kl_loss({'logit': heads(post['logit'])}, prior, **self.connector_kl)[1], None, 1.0)    # (kl_loss reads the logits only)
@@ -168,7 +181,7 @@ class VideoSSM(common.EnsembleRSSM):
             # (normalize + cosine_similarity + mean) as one node
             eps = noise.draw('normal', 'conn.clip_eps', video_embed.shape, dev)
             clean, embeds, actions_tm = ops.connector_prep(video_embed.to(dev), eps, nf, float(self.clip_lafite_noise),
-                                                           float(self.clip_const))
+                                                           float(self.clip_const), temporal=self.temporal_embeds)
             cosine_distance = ops.cosine_distance(self.aligner(embeds), clean)
             metrics['aligner_cosine_distance'] = cosine_distance
             loss = cosine_distance
@@ -185,7 +198,10 @@ class VideoSSM(common.EnsembleRSSM):
                 loss = cosine_distance
                 embeds = clean                                   # the SSM itself consumes the clean embedding
             actions_tm = self.get_action(embeds).transpose(0, 1).contiguous()
-        post = {k: v.reshape(B, T, *v.shape[2:]).detach() for k, v in wm_post.items()}
+        # (detached_post False: the connector trains end to end with the world model, the KL's posterior side and the teacher-forced
+        # stoch stay attached, :160-163)
+        held = (lambda v: v.detach()) if self.detached_post else (lambda v: v)
+        post = {k: held(v.reshape(B, T, *v.shape[2:])) for k, v in wm_post.items()}
         prior_logit = self._prior_under_teacher_forcing(actions_tm, post['stoch'], B, T)
         kl_loss, kl_value = self.kl_loss(post, {'logit': prior_logit}, **self.connector_kl)
         metrics['connector_kl'] = ops.wmean(kl_value.detach(), None, 1.0)

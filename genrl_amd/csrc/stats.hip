@@ -202,12 +202,13 @@ __global__ void normal_entropy_final_kernel(const double* __restrict__ part, int
 // ---- connector inputs (VideoSSM.update, agent/video_utils.py:127-161): one workgroup per (b, t) row of E floats
 //   clean[b,t]  = video[b, (t / nf) * nf + nf - 1]              (the embedding of the aligned nf-frame chunk)
 //   noisy[b,t]  = unit((1 - lam) * clean + lam * unit(eps))     ('lafite' noise; the aligner's input)
-//   act_tm[t,b] = [clean * cscale | 0 x nf]                     (the SSM's 'action', time-major)
+//   act_tm[t,b] = [clean * cscale | slots]                      (the SSM's 'action', time-major)
+// slots: nf zeros, or with `temporal` one_hot(t % nf) (`connector.temporal_embeds`, get_action :121).
 // F.normalize: x / max(||x||, 1e-12).
 __global__ __launch_bounds__(256) void connector_prep_kernel(const float* __restrict__ video, const float* __restrict__ eps,
                                                              float* __restrict__ clean, float* __restrict__ noisy,
                                                              float* __restrict__ act_tm, int B, int T, int E, int nf,
-                                                             float lam, float cscale) {
+                                                             float lam, float cscale, int temporal) {
   __shared__ float red[8];
   const int b = blockIdx.x / T, t = blockIdx.x % T;
   const float* src = video + ((long)b * T + (t / nf) * nf + nf - 1) * E;
@@ -228,7 +229,8 @@ __global__ __launch_bounds__(256) void connector_prep_kernel(const float* __rest
     ac[i] = c * cscale;
     sm += m * m;
   }
-  for (int i = threadIdx.x; i < nf; i += 256) ac[E + i] = 0.f;
+  const int slot = temporal ? t % nf : -1;
+  for (int i = threadIdx.x; i < nf; i += 256) ac[E + i] = i == slot ? 1.f : 0.f;
   sm = block_sum_256(sm, red);
   const float inv_m = 1.0f / fmaxf(sqrtf(sm), 1e-12f);
   for (int i = threadIdx.x; i < E; i += 256) no[i] *= inv_m;
@@ -276,6 +278,53 @@ __global__ __launch_bounds__(256) void cosdist_bwd_kernel(const float* __restric
   const float proj = rn >= 1e-8f ? cs / (rn * rn) : 0.f;
   const float k = -g[0] / (float)R / nx;
   for (int i = threadIdx.x; i < E; i += 256) dx[row * E + i] = k * (cr[i] * inv_c - proj * (xr[i] / nx));
+}
+
+// ---- teacher-forcing inputs under `connector.token_dropout` (VideoSSM.update, agent/video_utils.py:171-179): one workgroup per
+// time-major output row r = t * B + b of W floats.
+//   keep[t,b] = e[t,b] < thresh          (e ~ Exp(1): exp(-e) is uniform, so this is `rand > p` with thresh = -log p)
+//   x[t,b]    = keep * (t == 0 ? first[b] : post[b, t-1])      (post batch-major (B,T,W))
+// Values are copied or zeroed, never scaled: keep is exactly 0 or 1.  VEC: rows of float4 (W % 4 == 0 and aligned bases).
+template <bool VEC>
+__global__ __launch_bounds__(256) void tf_inputs_fwd_kernel(const float* __restrict__ first, const float* __restrict__ post,
+                                                            const float* __restrict__ e, float thresh, int B, int T, int W,
+                                                            float* __restrict__ x, float* __restrict__ keep) {
+  const long r = blockIdx.x;
+  const int t = (int)(r / B), b = (int)(r % B);
+  const bool k = e[r] < thresh;
+  if (threadIdx.x == 0) keep[r] = k ? 1.f : 0.f;
+  const float* src = t == 0 ? first + (long)b * W : post + ((long)b * T + (t - 1)) * W;
+  float* dst = x + r * W;
+  if (VEC) {
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = threadIdx.x; i < W / 4; i += 256)
+      reinterpret_cast<float4*>(dst)[i] = k ? reinterpret_cast<const float4*>(src)[i] : z;
+  } else {
+    for (int i = threadIdx.x; i < W; i += 256) dst[i] = k ? src[i] : 0.f;
+  }
+}
+// one workgroup per row r = t * B + b of g (T*B, W):  row (0, b) -> dfirst[b];  row (t >= 1, b) -> dpost[b, t-1] (when asked for);
+// the rows (T, b) past the end of g zero dpost[b, T-1] (grid: (T + 1) * B rows when dpost is written, B otherwise).
+template <bool VEC>
+__global__ __launch_bounds__(256) void tf_inputs_bwd_kernel(const float* __restrict__ g, const float* __restrict__ keep, int B,
+                                                            int T, int W, float* __restrict__ dfirst, float* __restrict__ dpost) {
+  const long r = blockIdx.x;
+  const int t = (int)(r / B), b = (int)(r % B);
+  float* dst = t == 0 ? dfirst + (long)b * W : dpost + ((long)b * T + (t - 1)) * W;
+  const bool k = t < T && keep[r] != 0.f;
+  const float* src = g + (t < T ? r : 0) * W;               // (not read when !k)
+  if (VEC) {
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = threadIdx.x; i < W / 4; i += 256)
+      reinterpret_cast<float4*>(dst)[i] = k ? reinterpret_cast<const float4*>(src)[i] : z;
+  } else {
+    for (int i = threadIdx.x; i < W; i += 256) dst[i] = k ? src[i] : 0.f;
+  }
+}
+
+// rows of W floats at these bases can go as float4: W % 4 == 0 and every (non-null) base 16-byte aligned
+bool rows_of_float4(int W, const void* a, const void* b, const void* c) {
+  return W % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
 }
 
 }  // namespace
@@ -347,10 +396,36 @@ int genrl_normal_entropy_mean(const float* raw, long R, int A, float min_std, fl
 
 int genrl_connector_prep(const float* video, const float* eps, float* clean, float* noisy, float* act_tm, int B, int T,
                          int E, int nf, float lam, float cscale, void* stream) {
+  return genrl_connector_prep_slots(video, eps, clean, noisy, act_tm, B, T, E, nf, lam, cscale, 0, stream);
+}
+
+int genrl_connector_prep_slots(const float* video, const float* eps, float* clean, float* noisy, float* act_tm, int B, int T,
+                               int E, int nf, float lam, float cscale, int temporal, void* stream) {
   GENRL_ENTER();
   if (B <= 0 || T <= 0 || E <= 0 || nf <= 0 || T % nf) return GENRL_EINVAL;
   hipLaunchKernelGGL(connector_prep_kernel, dim3(B * T), dim3(256), 0, (hipStream_t)stream, video, eps, clean, noisy, act_tm,
-                     B, T, E, nf, lam, cscale);
+                     B, T, E, nf, lam, cscale, temporal != 0);
+  GENRL_CHECK_LAUNCH();
+  return GENRL_OK;
+}
+
+int genrl_tf_inputs_fwd(const float* first, const float* post, const float* e, float thresh, int B, int T, int W, float* x,
+                        float* keep, void* stream) {
+  GENRL_ENTER();
+  if (B <= 0 || T <= 0 || W <= 0 || !first || !post || !e || !x || !keep) return GENRL_EINVAL;
+  auto kern = rows_of_float4(W, first, post, x) ? tf_inputs_fwd_kernel<true> : tf_inputs_fwd_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((long)T * B)), dim3(256), 0, (hipStream_t)stream, first, post, e, thresh, B, T, W, x,
+                     keep);
+  GENRL_CHECK_LAUNCH();
+  return GENRL_OK;
+}
+
+int genrl_tf_inputs_bwd(const float* g, const float* keep, int B, int T, int W, float* dfirst, float* dpost, void* stream) {
+  GENRL_ENTER();
+  if (B <= 0 || T <= 0 || W <= 0 || !g || !keep || !dfirst) return GENRL_EINVAL;
+  auto kern = rows_of_float4(W, g, dfirst, dpost) ? tf_inputs_bwd_kernel<true> : tf_inputs_bwd_kernel<false>;
+  const long rows = dpost ? (long)(T + 1) * B : B;
+  hipLaunchKernelGGL(kern, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, g, keep, B, T, W, dfirst, dpost);
   GENRL_CHECK_LAUNCH();
   return GENRL_OK;
 }

@@ -107,7 +107,9 @@ _ROWS_DIM1 = {'wm.post_q', 'wm.prior_q', 'imag.act_eps', 'imag.act_q', 'imag.ste
               # continuous latents ('normal'): (T, B, S) posterior / prior noise of a scan, (H, N, S) of an imagined rollout
               'wm.post_eps', 'wm.prior_eps', 'imag.step_eps', 'rssm.imagine_eps',
               # the tanh_normal head's Monte-Carlo draws: (K (H-1), N, A) entropy noise of the actor loss, (K, rows, A) of a mean
-              'actor.ent_eps', 'actor.mean_eps', 'imag.act_mean_eps'}
+              'actor.ent_eps', 'actor.mean_eps', 'imag.act_mean_eps',
+              # the connector's token dropout: (T, B) Exp(1) noise, one keep flag per step and row
+              'conn.drop'}
 
 
 @contextlib.contextmanager

@@ -876,15 +876,52 @@ def cosine_distance(x, c):
     return _CosDist.apply(x, c)
 
 
-def connector_prep(video, eps, nf, lam, cscale):
-    """-> clean (B,T,E), noisy (B,T,E), actions time-major (T,B,E+nf): VideoSSM.update's input preparation in one launch"""
+def connector_prep(video, eps, nf, lam, cscale, temporal=False):
+    """-> clean (B,T,E), noisy (B,T,E), actions time-major (T,B,E+nf): VideoSSM.update's input preparation in one launch.
+    temporal (`connector.temporal_embeds`): the nf slot columns of the actions hold one_hot(t % nf) instead of zeros"""
     v = _f32(video).contiguous(); e = _f32(eps).contiguous()
     B, T, E = v.shape
     clean, noisy = torch.empty_like(v), torch.empty_like(v)
     act = torch.empty(T, B, E + nf, device=v.device)
+    if temporal:
+        check(lib().genrl_connector_prep_slots(_p(v), _p(e), _p(clean), _p(noisy), _p(act), B, T, E, nf, lam, cscale, 1, _stream()),
+              'connector_prep_slots')
+        return clean, noisy, act
     check(lib().genrl_connector_prep(_p(v), _p(e), _p(clean), _p(noisy), _p(act), B, T, E, nf, lam, cscale, _stream()),
           'connector_prep')
     return clean, noisy, act
+
+
+class _TFInputs(Function):
+    @staticmethod
+    def forward(ctx, first, post, e, thresh):
+        f = _f32(first).contiguous(); po = _f32(post).contiguous(); e = _f32(e).contiguous()
+        B, T, W = po.shape
+        assert f.shape == (B, W) and e.shape == (T, B), (f.shape, po.shape, e.shape)
+        x, keep = torch.empty(T, B, W, device=po.device), torch.empty(T, B, device=po.device)
+        check(lib().genrl_tf_inputs_fwd(_p(f), _p(po), _p(e), thresh, B, T, W, _p(x), _p(keep), _stream()), 'tf_inputs_fwd')
+        ctx.save_for_backward(keep)
+        ctx.mark_non_differentiable(keep)
+        return x, keep
+
+    @staticmethod
+    def backward(ctx, g, _gk):
+        (keep,) = ctx.saved_tensors
+        T, B, W = g.shape
+        dfirst = torch.empty(B, W, device=g.device)
+        dpost = torch.empty(B, T, W, device=g.device) if ctx.needs_input_grad[1] else None
+        check(lib().genrl_tf_inputs_bwd(_p(g.contiguous()), _p(keep), B, T, W, _p(dfirst), _p(dpost), _stream()), 'tf_inputs_bwd')
+        return dfirst, dpost, None, None
+
+
+def tf_inputs(first, post, e, p):
+    """The connector's teacher-forced input under `connector.token_dropout: p` as one node: first (B,W) = stoch of the initial state,
+    post (B,T,W) = the world model's posterior stoch, e (T,B) ~ Exp(1)  ->  x (T,B,W) time-major with
+    x[t,b] = keep[t,b] * (first[b] if t == 0 else post[b,t-1]), and keep (T,B) = (e < -log p) as 0/1 floats: exp(-e) is uniform, so a row
+    is kept with probability 1 - p, as by the reference's `rand > p`.  Gradient to first, and to post where it asks for one."""
+    import math
+    assert 0 < p < 1, p
+    return _TFInputs.apply(first, post, e, -math.log(p))
 
 
 def wmean(x, w=None, scale=1.0):

@@ -676,10 +676,22 @@ int genrl_normal_entropy_mean(const float* raw, long R, int A, float min_std, fl
  * genrl_connector_prep: from the batch's clip embeddings video (B,T,E) and Gaussian noise eps (B,T,E): clean (B,T,E) = the
  *   embedding of each aligned nf-frame chunk held over the chunk (:134-136), noisy (B,T,E) = unit((1-lam) clean + lam unit(eps))
  *   (lafite noise, :141-145), act_tm (T,B,E+nf) = [clean * cscale | zeros] time-major (get_action, :114-125).
+ * genrl_connector_prep_slots: the same launch with the slot columns chosen: temporal 0 = zeros (what genrl_connector_prep passes),
+ *   non-zero = one_hot(t % nf) (`connector.temporal_embeds`, :121).
+ * genrl_tf_inputs_{fwd,bwd}: the teacher-forced input of the connector's prior pass under `connector.token_dropout` (:171-179).
+ *   fwd: first (B,W), post (B,T,W) batch-major, e (T,B) Exp(1) noise: keep (T,B) = e < thresh as 0/1 floats and
+ *   x (T*B,W) time-major, x[t*B+b] = keep[t,b] * (t == 0 ? first[b] : post[b,t-1]).
+ *   bwd: g (T*B,W): dfirst[b] = keep[0,b] g[0,b]; dpost (NULL: not written) [b,t] = keep[t+1,b] g[t+1,b], zero at t = T-1.
+ *   Any W; rows go as float4 where W % 4 == 0 and the bases are 16-byte aligned.
  * genrl_cosdist_{fwd,bwd}: the aligner's loss 1 - mean(cosine_similarity(normalize(x), c)) (:146-150), gradient to x;
  *   cosv, xnorm: R floats each, kept for the backward. */
 int genrl_connector_prep(const float* video, const float* eps, float* clean, float* noisy, float* act_tm, int B, int T,
                          int E, int nf, float lam, float cscale, void* stream);
+int genrl_connector_prep_slots(const float* video, const float* eps, float* clean, float* noisy, float* act_tm, int B, int T,
+                               int E, int nf, float lam, float cscale, int temporal, void* stream);
+int genrl_tf_inputs_fwd(const float* first, const float* post, const float* e, float thresh, int B, int T, int W, float* x,
+                        float* keep, void* stream);
+int genrl_tf_inputs_bwd(const float* g, const float* keep, int B, int T, int W, float* dfirst, float* dpost, void* stream);
 int genrl_cosdist_fwd(const float* x, const float* c, float* cosv, float* xnorm, float* out, long R, int E, void* stream);
 int genrl_cosdist_bwd(const float* x, const float* c, const float* cosv, const float* xnorm, const float* g, float* dx,
                       long R, int E, void* stream);
