@@ -1,4 +1,4 @@
-"""Helpers of the float64 kernel tests (test_gpu_row_kernel_variants.py, test_gpu_dist_optim_variants.py, test_gpu_plane_variants.py): per-element bounds
+"""Helpers of the float64 kernel tests (test_gpu_row_kernel_variants.py, test_gpu_dist_optim_variants.py, test_gpu_plane_variants.py, test_gpu_conv_loops.py): per-element bounds
 against a float64 reference, NaN-prefilled output buffers with padding columns and a guard row, and the check that a kernel
 wrote nothing outside its output."""
 import math

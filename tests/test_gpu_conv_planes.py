@@ -234,7 +234,7 @@ def test_direct_three_channel_transposed_convolution(N, Hi, Wi, Co, nchw, bwd, m
     def hip(x, W, b):
         return ops.convT2d_s2(x, W, b, out_nchw=nchw)
     assert ops.CONVT_DIRECT
-    monkeypatch.setattr(ops, 'CONVT_DIRECT_BWD', bwd)       # (the direct backward kernels are opt-in: measured slower; parity is pinned all the same)
+    monkeypatch.setattr(ops, 'CONVT_DIRECT_BWD', bwd)       # (the direct backward kernels are the default, ops.CONVT_DIRECT_BWD; both settings are pinned)
     y = hip(x.cuda(), W.cuda(), b.cuda())
     r = ref(x.double(), W.double(), b.double())
     assert y.shape == r.shape
